@@ -72,7 +72,60 @@ def parse_args():
                    help="validation mode: tiny opponents on CPU over gloo — "
                         "exercises the full multi-rank round flow (threaded "
                         "opponents, ordered consensus gathers) without GPUs")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed rounds, write what the LAST timed "
+                        "round returned (every opponent's critique token "
+                        "ids + agreed/error flags, as gathered for the "
+                        "consensus check, plus the ids the graphed decode "
+                        "sampled) to DIR/<name>.npy in float32")
+    p.add_argument("--full", action="store_true",
+                   help="also run the benchmark's secondary measurements. "
+                        "A plain run does only what the headline figure "
+                        "needs; bench.py has no secondary measurements "
+                        "today, so --full currently adds nothing")
     return p.parse_args()
+
+
+def dump_outputs(out_dir: str, results, all_agreed: bool,
+                 max_tokens: int, sampled=None) -> None:
+    """Write one round's gathered results as float32 .npy arrays.
+
+    One row per opponent of the whole job, in gather order (rank-major,
+    then opponent index). Token ids are exact in float32 (vocab < 2^24);
+    rows are padded with -1 past each critique's length. A few KB per
+    opponent, far below any size concern. Inputs (weights, prompt, sampler
+    seeds) are functions of the arguments alone, so two runs with the same
+    arguments are comparable array for array.
+
+    The gathered critique is the DETOKENIZED text re-encoded: with the
+    byte tokenizer of random-init opponents nearly every sampled id
+    (>= 256) carries no text, so those rows are a few tokens long.
+    `sampled` (rank 0's opponents, one id list each) is the decode's
+    token-for-token record behind that text and goes to
+    sampled_tokens.npy with the same padding.
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    n = len(results)
+    tokens = np.full((n, max_tokens), -1.0, dtype=np.float32)
+    for i, r in enumerate(results):
+        tokens[i, : len(r.token_ids)] = r.token_ids
+    arrays = {
+        "critique_tokens": tokens,
+        "critique_lengths": np.array([len(r.token_ids) for r in results],
+                                     dtype=np.float32),
+        "agreed": np.array([r.agreed for r in results], dtype=np.float32),
+        "error": np.array([r.error for r in results], dtype=np.float32),
+        "all_agreed": np.array([all_agreed], dtype=np.float32),
+    }
+    if sampled is not None:
+        st = np.full((len(sampled), max_tokens), -1.0, dtype=np.float32)
+        for i, ids in enumerate(sampled):
+            st[i, : len(ids)] = ids
+        arrays["sampled_tokens"] = st
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
 
 
 def main() -> int:
@@ -163,13 +216,15 @@ def main() -> int:
 
     pool = ThreadPoolExecutor(max_workers=max(1, n_opp))
 
+    n_out: dict[str, int] = {}  # tokens each opponent decoded last round
+
     def run_one(eng):
         # per-opponent fault isolation (reference semantics: an errored
         # opponent degrades the round, never aborts it — and on the
         # distributed path an un-launched collective would DEADLOCK the
         # other ranks, so errors must still reach the gather)
         try:
-            text, _in, _out, _tm = eng.generate(
+            text, _in, n_out[eng.name], _tm = eng.generate(
                 system_prompt,
                 user_message,
                 max_tokens=args.decode_tokens,
@@ -181,6 +236,7 @@ def main() -> int:
             return ids, agreed, False
         except Exception as e:  # noqa: BLE001
             print(f"opponent {eng.name} failed: {e}", file=sys.stderr)
+            n_out.pop(eng.name, None)
             return [], False, True
 
     def one_round():
@@ -191,6 +247,7 @@ def main() -> int:
         the decode GEMVs of N opponents interleave and fill HBM bandwidth
         that a single bandwidth-bound decode leaves idle. Collectives are
         still launched in opponent order (identical on every rank).
+        Returns (all_agreed, per-opponent results of the whole job).
         """
         local = []
         futures = [pool.submit(run_one, eng) for eng in engines]
@@ -210,15 +267,16 @@ def main() -> int:
                 r, ok = g.wait()
                 results.extend(r)
                 all_agreed = all_agreed and ok
-            return all_agreed
+            return all_agreed, results
         rows = torch.cat(local).view(n_opp, HDR + max_gather_tokens)
         results = unpack_results(rows)
         ok = [r for r in results if not r.error]
-        return bool(ok) and all(r.agreed for r in ok)
+        return bool(ok) and all(r.agreed for r in ok), results
 
     # warmup
     for _ in range(args.warmup):
         one_round()
+    last = None
 
     if dist is not None:
         dist.barrier()
@@ -226,12 +284,26 @@ def main() -> int:
         torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_round()
+        last = one_round()
     if dist is not None:
         dist.barrier()
     if use_gpu:
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+
+    if args.dump_outputs and rank == 0 and last is not None:
+        # The graphed decode (the GPU path outside --tp) leaves the ids it
+        # sampled in the captured graph's device-side history buffer; the
+        # host-stepped decode keeps no such record and the array is omitted.
+        sampled = []
+        for eng in engines:
+            gs = eng._graph_state
+            if gs is None or eng.name not in n_out:
+                sampled = None
+                break
+            sampled.append(gs["tok_hist"][: n_out[eng.name]].cpu().tolist())
+        dump_outputs(args.dump_outputs, last[1], last[0], max_gather_tokens,
+                     sampled)
 
     # max over ranks
     if dist is not None:

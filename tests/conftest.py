@@ -31,6 +31,21 @@ def isolated_paths(tmp_path, monkeypatch):
 
 
 @pytest.fixture
+def sock_dir(tmp_path, monkeypatch):
+    """Directory for unix sockets, as a path RELATIVE to the cwd.
+
+    AF_UNIX addresses hold at most 107 bytes, and pytest's tmp_path can
+    exceed that on its own when the temp root is deep. The test runs with
+    tmp_path as its working directory and names its sockets relative to
+    it, so the bound address is short wherever the suite runs.
+    """
+    from pathlib import Path
+
+    monkeypatch.chdir(tmp_path)
+    return Path(".")
+
+
+@pytest.fixture
 def clean_env(monkeypatch):
     """Strip provider keys / backend overrides from the environment."""
     for var in [

@@ -14,8 +14,8 @@ SPEC = "# Payments API\n\nA spec that needs critique."
 
 
 @pytest.fixture
-def live_daemon(tmp_path, monkeypatch):
-    sock = tmp_path / "d.sock"
+def live_daemon(sock_dir, monkeypatch):
+    sock = sock_dir / "d.sock"
     monkeypatch.setattr(daemon, "SOCKET_PATH", sock)
     srv = daemon.serve(sock)
     t = threading.Thread(target=srv.serve_forever, daemon=True)
@@ -88,8 +88,8 @@ class TestDaemonGuards:
         with pytest.raises(RuntimeError, match="already serving"):
             daemon.serve(sock)
 
-    def test_stale_socket_cleaned_up(self, tmp_path):
-        sock = tmp_path / "stale.sock"
+    def test_stale_socket_cleaned_up(self, sock_dir):
+        sock = sock_dir / "stale.sock"
         sock.touch()  # dead socket file, nothing listening
         srv = daemon.serve(sock)
         try:
@@ -97,10 +97,10 @@ class TestDaemonGuards:
         finally:
             srv.server_close()
 
-    def test_serve_creates_deep_socket_dir(self, tmp_path):
+    def test_serve_creates_deep_socket_dir(self, sock_dir):
         """serve() must mkdir the socket's parents (mutation killer:
         mkdir(parents=True) — a fresh install has no config dir)."""
-        sock = tmp_path / "a" / "b" / "daemon.sock"
+        sock = sock_dir / "a" / "b" / "daemon.sock"
         srv = daemon.serve(sock)
         try:
             assert sock.exists()

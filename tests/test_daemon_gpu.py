@@ -15,10 +15,10 @@ SPEC = "# Spec\n\nA small spec to critique."
 
 
 @pytest.mark.skipif(not torch.cuda.is_available(), reason="needs GPU")
-def test_daemon_round2_skips_engine_init(tmp_path, monkeypatch):
+def test_daemon_round2_skips_engine_init(sock_dir, monkeypatch):
     from adversarial_spec_amd import daemon
 
-    sock = tmp_path / "d.sock"
+    sock = sock_dir / "d.sock"
     monkeypatch.setattr(daemon, "SOCKET_PATH", sock)
     srv = daemon.serve(sock)
     t = threading.Thread(target=srv.serve_forever, daemon=True)
