@@ -84,7 +84,13 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(
   // ONE shared array (guide §5 trap 4a): [2 stage buffers][K | V] + the
   // q image. K images are chunk-swizzled; V and q are linear.
   constexpr int TILE_E = DTILE * (LPP * 8);          // elements per tile
-  constexpr int QIMG_E = MG * LPP * 8;
+  // The q image is written by whole-wave 16-B glds pieces (64 lanes x 8
+  // elements = 512 elements each, see below), so it is sized in whole
+  // pieces: MG*hd alone is under one piece for most instantiations and
+  // the DMA would land past the end of the array.
+  constexpr int QPIECE_E = WAVE * 8;
+  constexpr int QPIECES = (MG * LPP * 8 + QPIECE_E - 1) / QPIECE_E;
+  constexpr int QIMG_E = QPIECES * QPIECE_E;
   __shared__ __attribute__((aligned(16))) ushort_t lds[4 * TILE_E + QIMG_E];
   ushort_t *qlds = lds + 4 * TILE_E;
 
@@ -149,14 +155,14 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(
   typedef __attribute__((__vector_size__(8 * sizeof(short)))) short v8s;
   if (wid == 0) {
 #pragma unroll
-    for (int i = 0; i < (QIMG_E * 2 + 1023) / 1024; ++i) {
-      if (i * 512 >= group * hd) break;  // uniform: MG may exceed group
-      const int off8 = min(i * 512 + lane * 8, group * hd - 8);
+    for (int i = 0; i < QPIECES; ++i) {
+      if (i * QPIECE_E >= group * hd) break;  // uniform: MG may exceed group
+      const int off8 = min(i * QPIECE_E + lane * 8, group * hd - 8);
       __builtin_amdgcn_global_load_lds(
           (const __attribute__((address_space(1))) void
                *)(q + (size_t)(g * group) * hd + off8),
-          (__attribute__((address_space(3))) void *)(qlds + i * 512), 16, 0,
-          0);
+          (__attribute__((address_space(3))) void *)(qlds + i * QPIECE_E), 16,
+          0, 0);
     }
   }
 

@@ -390,6 +390,17 @@ static void split_geometry(long seq, int kh, int target_blocks,
   *split_len = sl;
 }
 
+// Geometry query for tests: the (n_splits, split_len) a decode call with
+// these arguments launches (ADVSPEC_SPLIT_BLOCKS override included), so a
+// test can assert the tile/split path it claims to exercise.
+py::tuple decode_split_geometry(int64_t seq, int64_t kh,
+                                int64_t split_blocks) {
+  TORCH_CHECK(seq >= 1 && kh >= 1, "decode_split_geometry: seq, kh >= 1");
+  int n_splits, split_len;
+  split_geometry(seq, (int)kh, (int)split_blocks, &n_splits, &split_len);
+  return py::make_tuple(n_splits, split_len);
+}
+
 torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kc,
                                 torch::Tensor vc, torch::Tensor page_table,
                                 int64_t seq_len, double scale,
@@ -863,6 +874,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
         py::arg("seq_len"), py::arg("scale"), py::arg("identity") = false,
         py::arg("split_blocks") = 0);
+  m.def("decode_split_geometry", &decode_split_geometry,
+        "decode split geometry query -> (n_splits, split_len)",
+        py::arg("seq"), py::arg("kh"), py::arg("split_blocks") = 0);
   m.def("sample", &sample, "fused temperature softmax sample");
   m.def("sample_to", &sample_to, "async on-device sample into out[idx]");
   m.def("gemv", &gemv, "batch-1 decode GEMV (weight streaming)",
