@@ -533,8 +533,15 @@ class LlamaModel:
         if not (fused_bf or fused_f8):
             ops.rmsnorm(W.resid, self.layers[0].attn_norm, c.norm_eps,
                         out=W.normed)
+        # RoPE + KV append ride in the qkv GEMV's epilogue (one launch, no
+        # qkv round trip) wherever the w32 row geometry holds; the
+        # ADVSPEC_FP8_LDS path, TP and odd shapes keep the rope_kv launch
+        # (every layer's cache is a slice of one tensor: layer 0 speaks for all)
+        fuse_rope = ops.qkv_rope_fusable(h, kh, hd, self.cos, self.sin,
+                                         cache.k[0], cache.v[0])
         for i, L in enumerate(self.layers):
             Qd = self.layers_q[i] if fp8 else None
+            roped = False
             if fused_f8:
                 qw = Qd.get("wqkv")
                 if _FP8_LDS:
@@ -543,17 +550,33 @@ class LlamaModel:
                 else:
                     ops.quant_norm_fp8(W.resid, L.attn_norm, W.x8, W.xs,
                                        c.norm_eps)
-                    ops.gemv_fp8_q(W.x8, W.xs, qw.q, qw.s, W.qkv)
+                    if fuse_rope:
+                        ops.gemv_fp8_q_rope_kv(
+                            W.x8, W.xs, qw.q, qw.s, W.qkv, self.cos, self.sin,
+                            cache.k[i], cache.v[i], cache.page_table, 0, h,
+                            kh, pos_state=pos_state)
+                        roped = True
+                    else:
+                        ops.gemv_fp8_q(W.x8, W.xs, qw.q, qw.s, W.qkv)
             elif fused_bf:
-                ops.gemv_norm(W.resid, L.attn_norm, L.wqkv, c.norm_eps,
-                              out=W.qkv)
+                if fuse_rope:
+                    ops.gemv_norm_rope_kv(
+                        W.resid, L.attn_norm, L.wqkv, c.norm_eps, self.cos,
+                        self.sin, cache.k[i], cache.v[i], cache.page_table, 0,
+                        h, kh, pos_state=pos_state, out=W.qkv)
+                    roped = True
+                else:
+                    ops.gemv_norm(W.resid, L.attn_norm, L.wqkv, c.norm_eps,
+                                  out=W.qkv)
             else:
                 proj(W.normed, L, Qd, "wqkv", W.qkv)
             q = W.qkv[:, : h * hd].view(1, h, hd)
-            k = W.qkv[:, h * hd : (h + kh) * hd].view(1, kh, hd)
-            v = W.qkv[:, (h + kh) * hd :].view(1, kh, hd)
-            ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i], cache.v[i],
-                        cache.page_table, 0, pos_state=pos_state)
+            if not roped:
+                k = W.qkv[:, h * hd : (h + kh) * hd].view(1, kh, hd)
+                v = W.qkv[:, (h + kh) * hd :].view(1, kh, hd)
+                ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i],
+                            cache.v[i], cache.page_table, 0,
+                            pos_state=pos_state)
             ops.attn_decode_paged(
                 q[0], cache.k[i], cache.v[i], cache.page_table,
                 max_seq_bound, self.scale, pos_state=pos_state, out=W.attn,

@@ -234,6 +234,103 @@ def gemv_norm(x: torch.Tensor, wln: torch.Tensor, w: torch.Tensor, eps: float,
     return y
 
 
+def qkv_rope_fusable(hq: int, kh: int, hd: int,
+                     cos: Optional[torch.Tensor] = None,
+                     sin: Optional[torch.Tensor] = None,
+                     k_cache: Optional[torch.Tensor] = None,
+                     v_cache: Optional[torch.Tensor] = None) -> bool:
+    """Whether the fused qkv + RoPE + KV-append GEMVs accept this call: the
+    w32 row geometry (one rotation pair per wave) and, for the tensors that
+    are passed, everything their binding insists on (f32 contiguous
+    [max_pos, hd/2] tables, contiguous [n_pages, page, kh, hd] caches).
+    Anything else runs the GEMV followed by rope_kv."""
+    if hd % 16 != 0 or (hq + 2 * kh) * hd > 8192:
+        return False
+    for t in (cos, sin):
+        if t is not None and not (
+            t.dtype == torch.float32 and t.dim() == 2 and t.is_contiguous()
+            and t.shape[1] == hd // 2
+        ):
+            return False
+    if cos is not None and sin is not None and cos.shape != sin.shape:
+        return False
+    for t in (k_cache, v_cache):
+        if t is not None and not (
+            t.dtype == torch.bfloat16 and t.dim() == 4 and t.is_contiguous()
+            and t.shape[2] == kh and t.shape[3] == hd
+        ):
+            return False
+    if (k_cache is not None and v_cache is not None
+            and k_cache.shape != v_cache.shape):
+        return False
+    return True
+
+
+def _rope_kv_on_qkv(y: torch.Tensor, hq: int, kh: int, cos, sin, k_cache,
+                    v_cache, page_table, pos0: int, pos_state) -> torch.Tensor:
+    """CPU composition shared by the fused qkv ops: rope_kv on the q/k/v
+    views of the projected row y [1, (hq+2*kh)*hd], written back into y."""
+    hd = y.numel() // (hq + 2 * kh)
+    if pos_state is not None:
+        pos0 = int(pos_state.reshape(-1)[0])
+    row = y.view(1, -1)
+    q = row[:, : hq * hd].view(1, hq, hd)
+    k = row[:, hq * hd : (hq + kh) * hd].view(1, kh, hd)
+    v = row[:, (hq + kh) * hd :].view(1, kh, hd)
+    q2, k2 = rope_kv(q, k, v, cos, sin, k_cache, v_cache, page_table, pos0)
+    q.copy_(q2)
+    k.copy_(k2)
+    return y
+
+
+def gemv_norm_rope_kv(
+    x: torch.Tensor, wln: torch.Tensor, w: torch.Tensor, eps: float,
+    cos: torch.Tensor, sin: torch.Tensor, k_cache: torch.Tensor,
+    v_cache: torch.Tensor, page_table: torch.Tensor, pos0: int,
+    hq: int, kh: int, pos_state: Optional[torch.Tensor] = None,
+    out: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """Decode fusion: qkv = rmsnorm(x, wln) @ w^T with RoPE on the q/k
+    heads and the rotated k plus v appended to the paged cache at `pos0`
+    (`pos_state` in graph mode), in ONE launch. w is the fused [q|k|v]
+    projection, (hq + 2*kh)*hd rows. Bit-identical to gemv_norm followed by
+    rope_kv on the views of its output; returns that output [1, N]."""
+    if _on_gpu(x):
+        return _require_hip().gemv_norm_rope_kv(
+            x, wln, w, eps, cos, sin, k_cache, v_cache, page_table, pos0,
+            hq, kh, pos_state, out)
+    y = gemv_norm(x, wln, w, eps).reshape(1, -1).contiguous()
+    _rope_kv_on_qkv(y, hq, kh, cos, sin, k_cache, v_cache, page_table, pos0,
+                    pos_state)
+    if out is not None:
+        out.copy_(y.reshape(out.shape))
+        return out
+    return y
+
+
+def gemv_fp8_q_rope_kv(
+    x8: torch.Tensor, xs: torch.Tensor, w_q: torch.Tensor,
+    w_scale: torch.Tensor, out: torch.Tensor, cos: torch.Tensor,
+    sin: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+    page_table: torch.Tensor, pos0: int, hq: int, kh: int,
+    pos_state: Optional[torch.Tensor] = None,
+) -> torch.Tensor:
+    """fp8 twin of gemv_norm_rope_kv: pre-quantized x8/xs (quant_norm_fp8)
+    against the rowwise-e4m3 fused qkv weight. Bit-identical to gemv_fp8_q
+    followed by rope_kv."""
+    if x8.is_cuda:
+        _require_hip().gemv_fp8_q_rope_kv(
+            x8, xs, w_q, w_scale, out, cos, sin, k_cache, v_cache,
+            page_table, pos0, hq, kh, pos_state)
+        return out
+    y = torch.empty(1, w_q.shape[0], dtype=out.dtype)
+    gemv_fp8_q(x8, xs, w_q, w_scale, y)
+    _rope_kv_on_qkv(y, hq, kh, cos, sin, k_cache, v_cache, page_table, pos0,
+                    pos_state)
+    out.copy_(y.reshape(out.shape))
+    return out
+
+
 def gemv_res(x: torch.Tensor, w: torch.Tensor, resid: torch.Tensor) -> torch.Tensor:
     """Decode fusion: resid += x @ w^T in place (the producing GEMV's
     epilogue adds the residual, so the delta never materializes). NOT valid

@@ -303,6 +303,27 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(
 // (62% wave-parked) — as costly as the split pass itself.
 // ---------------------------------------------------------------------------
 
+// The combine's rescale-accumulate step with its roundings spelled out.
+// Written as `L += l * sc; A += a * sc`, hipcc's fp contraction depended on
+// the surrounding code: the unrolled rounds of 4 multiplied and added L in
+// two roundings (packed multiply, scalar adds) and fused A, the ragged loop
+// fused both. These helpers pin exactly that, so every walk over the splits
+// below produces the same bits whatever the compiler makes of its shape.
+DEVINL void combine_step_round(float &L, float &A, float l, float a,
+                               float sc) {
+  {
+#pragma clang fp contract(off)
+    L = L + l * sc;
+  }
+  A = __builtin_fmaf(a, sc, A);
+}
+
+DEVINL void combine_step_ragged(float &L, float &A, float l, float a,
+                                float sc) {
+  L = __builtin_fmaf(l, sc, L);
+  A = __builtin_fmaf(a, sc, A);
+}
+
 extern "C" __global__ void __launch_bounds__(256)
 attn_decode_combine_kernel(const float *__restrict__ ws_m,
                            const float *__restrict__ ws_l,
@@ -318,49 +339,98 @@ attn_decode_combine_kernel(const float *__restrict__ ws_m,
   __shared__ float red[4];
   __shared__ float redL[4];
 
-  // pass 1: global max over this wave's split stride (4 independent max
-  // chains — a serial walk exposed full cross-XCD latency per entry)
-  float m = -INFINITY;
-  {
+  float L = 0.f, Au[4] = {0.f, 0.f, 0.f, 0.f};
+  if (n_splits <= 64) {
+    // ONE memory round trip: this wave's <= 16 splits (s = sg + 4*j) have
+    // all of their m, l and acc words issued up front, so the kernel pays
+    // the cross-XCD latency once instead of once per pass (pass 2's loads
+    // used to wait behind the barrier that publishes M). Loads are
+    // unconditional on a clamped split index — a per-element "load or
+    // constant" select makes hipcc branch around every load and drain
+    // vmcnt per element; validity is applied to the arithmetic only.
+    // Arithmetic and accumulation order are those of the two-pass walk
+    // below (full rounds of 4 -> Au[u], the ragged last round -> Au[0], L
+    // in split order, the same combine_step_* roundings), so the output is
+    // bit-identical to it.
+    float mw[16], lw[16], aw[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      const int sc = min(sg + 4 * j, n_splits - 1);
+      const size_t b = ((size_t)g * n_splits + sc) * group + gi;
+      mw[j] = ws_m[b];
+      lw[j] = ws_l[b];
+      aw[j] = ws_acc[b * hd + dd];
+    }
     float m4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (sg + 4 * j < n_splits) m4[j & 3] = fmaxf(m4[j & 3], mw[j]);
+    const float m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[sg] = m;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      if (sg + 16 * r + 12 < n_splits) {  // wave-uniform: a full round
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = 4 * r + u;
+          const float sc = (mw[j] == -INFINITY) ? 0.f : exp2f(mw[j] - M);
+          combine_step_round(L, Au[u], lw[j], aw[j], sc);
+        }
+      } else {  // the ragged last round (and the empty ones after it)
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+          const int j = 4 * r + u;
+          if (sg + 4 * j < n_splits) {
+            const float sc = (mw[j] == -INFINITY) ? 0.f : exp2f(mw[j] - M);
+            combine_step_ragged(L, Au[0], lw[j], aw[j], sc);
+          }
+        }
+      }
+    }
+  } else {
+    // pass 1: global max over this wave's split stride (4 independent max
+    // chains — a serial walk exposed full cross-XCD latency per entry)
+    float m = -INFINITY;
+    {
+      float m4[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+      int s = sg;
+      for (; s + 12 < n_splits; s += 16) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          m4[u] = fmaxf(m4[u],
+                        ws_m[((size_t)g * n_splits + s + 4 * u) * group + gi]);
+      }
+      for (; s < n_splits; s += 4)
+        m4[0] = fmaxf(m4[0], ws_m[((size_t)g * n_splits + s) * group + gi]);
+      m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
+    }
+    if ((threadIdx.x & (WAVE - 1)) == 0) red[sg] = m;
+    __syncthreads();
+    const float M = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+
+    // pass 2: strided L/acc accumulation, 4 independent accumulators per
+    // wave (16 concurrent loads across the block) — the ws round-trip is
+    // cross-XCD latency-bound, so ILP depth is the lever
+    // ws_m holds the split kernel's LOG2-SCALED running max (m2 domain):
+    // rescale factors are exp2, not exp
     int s = sg;
     for (; s + 12 < n_splits; s += 16) {
 #pragma unroll
-      for (int u = 0; u < 4; ++u)
-        m4[u] = fmaxf(m4[u],
-                      ws_m[((size_t)g * n_splits + s + 4 * u) * group + gi]);
+      for (int u = 0; u < 4; ++u) {
+        const size_t b = ((size_t)g * n_splits + s + 4 * u) * group + gi;
+        const float mw = ws_m[b];
+        const float sc = (mw == -INFINITY) ? 0.f : exp2f(mw - M);
+        combine_step_round(L, Au[u], ws_l[b], ws_acc[b * hd + dd], sc);
+      }
     }
-    for (; s < n_splits; s += 4)
-      m4[0] = fmaxf(m4[0], ws_m[((size_t)g * n_splits + s) * group + gi]);
-    m = fmaxf(fmaxf(m4[0], m4[1]), fmaxf(m4[2], m4[3]));
-  }
-  if ((threadIdx.x & (WAVE - 1)) == 0) red[sg] = m;
-  __syncthreads();
-  const float M = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-
-  // pass 2: strided L/acc accumulation, 4 independent accumulators per
-  // wave (16 concurrent loads across the block) — the ws round-trip is
-  // cross-XCD latency-bound, so ILP depth is the lever
-  // ws_m holds the split kernel's LOG2-SCALED running max (m2 domain):
-  // rescale factors are exp2, not exp
-  float L = 0.f, Au[4] = {0.f, 0.f, 0.f, 0.f};
-  int s = sg;
-  for (; s + 12 < n_splits; s += 16) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const size_t b = ((size_t)g * n_splits + s + 4 * u) * group + gi;
+    for (; s < n_splits; s += 4) {
+      const size_t b = ((size_t)g * n_splits + s) * group + gi;
       const float mw = ws_m[b];
       const float sc = (mw == -INFINITY) ? 0.f : exp2f(mw - M);
-      L += ws_l[b] * sc;
-      Au[u] += ws_acc[b * hd + dd] * sc;
+      combine_step_ragged(L, Au[0], ws_l[b], ws_acc[b * hd + dd], sc);
     }
-  }
-  for (; s < n_splits; s += 4) {
-    const size_t b = ((size_t)g * n_splits + s) * group + gi;
-    const float mw = ws_m[b];
-    const float sc = (mw == -INFINITY) ? 0.f : exp2f(mw - M);
-    L += ws_l[b] * sc;
-    Au[0] += ws_acc[b * hd + dd] * sc;
   }
   float A = (Au[0] + Au[1]) + (Au[2] + Au[3]);
 

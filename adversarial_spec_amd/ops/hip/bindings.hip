@@ -52,6 +52,15 @@ void launch_gemv_gateup(const ushort_t*, const ushort_t*, ushort_t*, int, int,
                         hipStream_t);
 void launch_gemv_norm(const ushort_t*, const ushort_t*, const ushort_t*,
                       ushort_t*, int, int, float, hipStream_t);
+void launch_gemv_norm_rope_kv(const ushort_t*, const ushort_t*,
+                              const ushort_t*, ushort_t*, int, float,
+                              const float*, const float*, ushort_t*, ushort_t*,
+                              const int*, const int*, int, int, int, int, int,
+                              hipStream_t);
+void launch_gemv_fp8_rope_kv(const uint8_t*, const float*, const uint8_t*,
+                             const float*, ushort_t*, int, const float*,
+                             const float*, ushort_t*, ushort_t*, const int*,
+                             const int*, int, int, int, int, int, hipStream_t);
 void launch_gemv_res(const ushort_t*, const ushort_t*, ushort_t*, int, int,
                      hipStream_t);
 void launch_gemv_gateup_norm(const ushort_t*, const ushort_t*, const ushort_t*,
@@ -511,6 +520,122 @@ torch::Tensor gemv_norm(torch::Tensor x, torch::Tensor wln, torch::Tensor w,
   return y;
 }
 
+// Preconditions shared by the two qkv GEMVs whose epilogue rotates and
+// appends to the KV cache (rope_epilogue.h). Returns (hd, page, pos_ptr);
+// a shape outside them belongs on the gemv + rope_kv pair.
+struct RopeKvGeom { int hd, page; const int* pos_ptr; };
+static RopeKvGeom check_rope_kv_epilogue(
+    const char* op, int N, int64_t hq, int64_t kh, const torch::Tensor& cost,
+    const torch::Tensor& sint, const torch::Tensor& kc,
+    const torch::Tensor& vc, const torch::Tensor& page_table, int64_t pos0,
+    const c10::optional<torch::Tensor>& pos_state, const torch::Tensor& y) {
+  TORCH_CHECK(hq >= 1 && kh >= 1 && N % (hq + 2 * kh) == 0, op,
+              ": N == (hq + 2*kh)*hd");
+  const int hd = N / (int)(hq + 2 * kh);
+  TORCH_CHECK(hd % 16 == 0, op, ": hd % 16 == 0");
+  TORCH_CHECK(N <= 8192, op, ": w32 geometry only (N <= 8192)");
+  TORCH_CHECK(cost.is_cuda() && sint.is_cuda() &&
+                  cost.scalar_type() == at::kFloat &&
+                  sint.scalar_type() == at::kFloat,
+              op, ": cos/sin tables f32 on GPU");
+  TORCH_CHECK(cost.dim() == 2 && cost.is_contiguous() &&
+                  sint.is_contiguous() && cost.sizes() == sint.sizes() &&
+                  cost.size(1) == hd / 2,
+              op, ": cos/sin tables [max_pos, hd/2] contiguous");
+  CHECK_BF16_CUDA(kc);
+  CHECK_BF16_CUDA(vc);
+  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), op,
+              ": caches contiguous");
+  TORCH_CHECK(kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(2) == kh &&
+                  kc.size(3) == hd,
+              op, ": caches [n_pages, page, kh, hd]");
+  TORCH_CHECK(page_table.is_cuda() && page_table.scalar_type() == at::kInt &&
+                  page_table.is_contiguous(),
+              op, ": page_table int32 on GPU");
+  const int page = kc.size(1);
+  const int* pp = nullptr;
+  if (pos_state.has_value()) {
+    TORCH_CHECK(pos_state->is_cuda() && pos_state->scalar_type() == at::kInt &&
+                    pos_state->numel() >= 1,
+                op, ": pos_state int32 word on GPU");
+    pp = pos_state->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos0 >= 0 && pos0 < cost.size(0) &&
+                    pos0 / page < page_table.numel(),
+                op, ": pos inside the rope table and the page table");
+  }
+  CHECK_BF16_CUDA(y);
+  TORCH_CHECK(y.is_contiguous() && (long)y.numel() == (long)N, op,
+              ": out contiguous, numel == N");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(y.data_ptr()) % 4 == 0, op,
+              ": out 4-byte aligned (pairs are stored as one word)");
+  return {hd, page, pp};
+}
+
+// qkv projection + RoPE + KV append in one launch (bf16 weights):
+//   y = rmsnorm(x, wln) @ w^T, then q/k pairs rotated at pos, rotated k and
+//   v written to the cache row of pos — bit-identical to gemv_norm followed
+//   by rope_kv on the q/k/v views of y.
+torch::Tensor gemv_norm_rope_kv(
+    torch::Tensor x, torch::Tensor wln, torch::Tensor w, double eps,
+    torch::Tensor cost, torch::Tensor sint, torch::Tensor kc, torch::Tensor vc,
+    torch::Tensor page_table, int64_t pos0, int64_t hq, int64_t kh,
+    const c10::optional<torch::Tensor>& pos_state,
+    c10::optional<torch::Tensor> out_opt) {
+  CHECK_BF16_CUDA(x);
+  CHECK_BF16_CUDA(wln);
+  CHECK_BF16_CUDA(w);
+  TORCH_CHECK(w.dim() == 2 && w.is_contiguous());
+  const int N = w.size(0), K = w.size(1);
+  TORCH_CHECK((long)x.numel() == (long)K, "gemv_norm_rope_kv: x numel == K");
+  TORCH_CHECK((long)wln.numel() == (long)K,
+              "gemv_norm_rope_kv: wln numel == K");
+  TORCH_CHECK(K % 8 == 0, "gemv_norm_rope_kv: K % 8 == 0");
+  TORCH_CHECK(K <= 32768, "gemv_norm_rope_kv: LDS xl staging caps K at 32768");
+  auto xc = x.contiguous();
+  auto lc = wln.contiguous();
+  auto y = out_opt.has_value() ? *out_opt : torch::empty({1, N}, x.options());
+  const RopeKvGeom g = check_rope_kv_epilogue(
+      "gemv_norm_rope_kv", N, hq, kh, cost, sint, kc, vc, page_table, pos0,
+      pos_state, y);
+  launch_gemv_norm_rope_kv(uptr(xc), uptr(lc), uptr(w), uptr_mut(y), K,
+                           (float)eps, cost.data_ptr<float>(),
+                           sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
+                           page_table.data_ptr<int>(), g.pos_ptr, (int)pos0,
+                           (int)hq, (int)kh, g.hd, g.page, cur_stream());
+  return y;
+}
+
+// fp8 twin: pre-quantized x8/xs (quant_norm_fp8) against rowwise-e4m3 w8 —
+// bit-identical to gemv_fp8_q followed by rope_kv.
+void gemv_fp8_q_rope_kv(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
+                        torch::Tensor wsc, torch::Tensor out,
+                        torch::Tensor cost, torch::Tensor sint,
+                        torch::Tensor kc, torch::Tensor vc,
+                        torch::Tensor page_table, int64_t pos0, int64_t hq,
+                        int64_t kh,
+                        const c10::optional<torch::Tensor>& pos_state) {
+  TORCH_CHECK(w8.dim() == 2 && w8.is_contiguous() && w8.is_cuda() &&
+              w8.scalar_type() == at::kByte);
+  const int N = w8.size(0), K = w8.size(1);
+  TORCH_CHECK(K % 16 == 0, "gemv_fp8_q_rope_kv: K % 16 == 0");
+  TORCH_CHECK(x8.is_cuda() && x8.numel() >= K &&
+              x8.scalar_type() == at::kByte && x8.is_contiguous());
+  TORCH_CHECK(xs.is_cuda() && xs.numel() >= 1 &&
+              xs.scalar_type() == at::kFloat);
+  TORCH_CHECK(wsc.is_cuda() && wsc.numel() >= N &&
+              wsc.scalar_type() == at::kFloat && wsc.is_contiguous());
+  const RopeKvGeom g = check_rope_kv_epilogue(
+      "gemv_fp8_q_rope_kv", N, hq, kh, cost, sint, kc, vc, page_table, pos0,
+      pos_state, out);
+  launch_gemv_fp8_rope_kv(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
+                          w8.data_ptr<uint8_t>(), wsc.data_ptr<float>(),
+                          uptr_mut(out), K, cost.data_ptr<float>(),
+                          sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
+                          page_table.data_ptr<int>(), g.pos_ptr, (int)pos0,
+                          (int)hq, (int)kh, g.hd, g.page, cur_stream());
+}
+
 // residual-add fused into the GEMV epilogue: resid += x @ w^T (in place).
 // NOT valid under TP (the all-reduce needs the raw partial product).
 void gemv_res(torch::Tensor x, torch::Tensor w, torch::Tensor resid) {
@@ -912,6 +1037,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cost"),
         py::arg("sint"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
         py::arg("pos0"), py::arg("pos_state") = py::none());
+  m.def("gemv_norm_rope_kv", &gemv_norm_rope_kv,
+        "rmsnorm + qkv GEMV + RoPE + KV append, one launch (decode fusion)",
+        py::arg("x"), py::arg("wln"), py::arg("w"), py::arg("eps"),
+        py::arg("cost"), py::arg("sint"), py::arg("kc"), py::arg("vc"),
+        py::arg("page_table"), py::arg("pos0"), py::arg("hq"), py::arg("kh"),
+        py::arg("pos_state") = py::none(), py::arg("out") = py::none());
+  m.def("gemv_fp8_q_rope_kv", &gemv_fp8_q_rope_kv,
+        "pre-quantized fp8 qkv GEMV + RoPE + KV append, one launch",
+        py::arg("x8"), py::arg("xs"), py::arg("w8"), py::arg("wsc"),
+        py::arg("out"), py::arg("cost"), py::arg("sint"), py::arg("kc"),
+        py::arg("vc"), py::arg("page_table"), py::arg("pos0"), py::arg("hq"),
+        py::arg("kh"), py::arg("pos_state") = py::none());
   m.def("kv_write_ds", &kv_write_ds, "graph-mode KV scatter (device pos)");
   m.def("attn_decode_paged_ds", &attn_decode_paged_ds,
         "graph-mode paged decode attention (device pos)",

@@ -32,6 +32,25 @@ DEVINL ushort_t f32_to_bf16(float f) {
   return (ushort_t)(c.i >> 16);
 }
 
+// RoPE rotation of one interleaved (even, odd) pair by (cos, sin), packed
+// back as two bf16. Written as `ev*c - od*s` and `ev*s + od*c`, which of
+// the two products hipcc fused into the fma depended on the surrounding
+// kernel, and the other rounding shows once in ~2^15 bf16 results. The
+// roundings are spelled out (od's products round first, ev's are fused) so
+// every kernel that rotates, standalone or as a GEMV epilogue, gives the
+// same bits.
+DEVINL uint32_t rope_rotate_pair(float ev, float od, float c, float s) {
+  float od_s, od_c;
+  {
+#pragma clang fp contract(off)
+    od_s = od * s;
+    od_c = od * c;
+  }
+  const float e2 = __builtin_fmaf(ev, c, -od_s);
+  const float o2 = __builtin_fmaf(ev, s, od_c);
+  return (uint32_t)f32_to_bf16(e2) | ((uint32_t)f32_to_bf16(o2) << 16);
+}
+
 // 8 bf16 packed in 16 bytes (one dwordx4 load)
 struct bf16x8 { ushort_t u[8]; };
 struct f32x8  { float v[8]; };

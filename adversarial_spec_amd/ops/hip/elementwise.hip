@@ -192,8 +192,7 @@ rope_kv_kernel(ushort_t *__restrict__ q, ushort_t *__restrict__ k,
     float ev = bf16_to_f32((ushort_t)(pair & 0xffffu));
     float od = bf16_to_f32((ushort_t)(pair >> 16));
     float c = crow[p], s = srow[p];
-    const uint32_t rot = (uint32_t)f32_to_bf16(ev * c - od * s) |
-                         ((uint32_t)f32_to_bf16(ev * s + od * c) << 16);
+    const uint32_t rot = rope_rotate_pair(ev, od, c, s);
     ((uint32_t *)base)[p] = rot;
     if (cache_dst) cache_dst[p] = rot;
   }

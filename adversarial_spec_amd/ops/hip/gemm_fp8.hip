@@ -15,6 +15,7 @@
 // 8 fp8 = 8 B per lane read as the low/high half of a swizzled 16 B chunk.
 
 #include "common.h"
+#include "rope_epilogue.h"
 
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;
 typedef __attribute__((__vector_size__(2 * sizeof(float)))) float f32x2v;
@@ -402,6 +403,64 @@ gemv_fp8_kernel_w32(const uint8_t *__restrict__ x, const float *__restrict__ xs,
 #pragma unroll
   for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
   if (sl == 0) y[n] = f32_to_bf16(acc * xs[0] * wsc[n]);
+}
+
+// fp8 twin of gemv_norm_rope_kv_w32_kernel (gemv.hip): gemv_fp8_kernel_w32's
+// weight loop with the RoPE + KV-append store of rope_epilogue.h. Same
+// preconditions: N == (hq + 2*kh)*hd, hd % 16 == 0 (so N % 8 == 0).
+extern "C" __global__ void __launch_bounds__(256)
+gemv_fp8_rope_kv_w32_kernel(const uint8_t *__restrict__ x,
+                            const float *__restrict__ xs,
+                            const uint8_t *__restrict__ w,
+                            const float *__restrict__ wsc,
+                            ushort_t *__restrict__ y, int K, RopeKvArgs ra) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const int rg = lane >> 5;
+  const int sl = lane & 31;
+  const int n_even = blockIdx.x * 8 + wid * 2;
+  const int n = n_even + rg;
+
+  // epilogue operands first: their latency hides under the weight stream
+  const RopeKvPre pre = rope_kv_prefetch(ra, n_even);
+  const float ws_n = wsc[n];
+
+  const uint8_t *wr = w + (size_t)n * K;
+  const int nc = K / 16;
+
+  float acc = 0.f;
+  int c = sl;
+  for (; c + 96 < nc; c += 128) {
+    uint4 wv[4], xv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      wv[u] = *(const uint4 *)(wr + (size_t)(c + 32 * u) * 16);
+      xv[u] = *(const uint4 *)(x + (size_t)(c + 32 * u) * 16);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) acc += dot16_fp8(xv[u], wv[u]);
+  }
+  for (; c < nc; c += 32) {
+    const uint4 wv = *(const uint4 *)(wr + (size_t)c * 16);
+    const uint4 xv = *(const uint4 *)(x + (size_t)c * 16);
+    acc += dot16_fp8(xv, wv);
+  }
+
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
+  rope_kv_store(pre, y, n_even, acc * xs[0] * ws_n, lane);
+}
+
+extern "C" void launch_gemv_fp8_rope_kv(
+    const uint8_t *x, const float *xs, const uint8_t *w, const float *wsc,
+    ushort_t *y, int K, const float *cost, const float *sint, ushort_t *kc,
+    ushort_t *vc, const int *page_table, const int *pos_ptr, int pos, int hq,
+    int kh, int hd, int page, hipStream_t stream) {
+  const int N = (hq + 2 * kh) * hd;  // caller checked: hd % 16 == 0, N <= 8192
+  const RopeKvArgs ra = {cost, sint, kc, vc, page_table, pos_ptr,
+                         pos,  hq,   kh, hd, page};
+  gemv_fp8_rope_kv_w32_kernel<<<dim3(N / 8), 256, 0, stream>>>(x, xs, w, wsc,
+                                                               y, K, ra);
 }
 
 extern "C" void launch_gemv_fp8(const uint8_t *x, const float *xs,

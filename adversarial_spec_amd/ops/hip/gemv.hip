@@ -14,6 +14,7 @@
 // slowdown in round 1).
 
 #include "common.h"
+#include "rope_epilogue.h"
 // dot8_bf16 (packed v_dot2_f32_bf16 row dot) comes from common.h
 
 // 16-lane-group sum (lanes p, p+1, .., p+15 with stride 1)
@@ -253,6 +254,52 @@ gemv_norm_w32_kernel(const ushort_t *__restrict__ x,
   if (sl == 0 && n0 < N) y[n0] = f32_to_bf16(acc * rms);
 }
 
+// qkv projection + RoPE + KV append in ONE launch: gemv_norm_w32_kernel's
+// prologue and weight loop, with rope_epilogue.h as the store. Removes the
+// rope_kv launch (a latency-bound tiny grid, 2x slower on a loaded memory
+// system) and the qkv round trip from every layer of the decode chain.
+// Requires N == (hq + 2*kh)*hd with hd % 16 == 0, so N % 8 == 0 and no row
+// of the grid is out of range.
+extern "C" __global__ void __launch_bounds__(256)
+gemv_norm_rope_kv_w32_kernel(const ushort_t *__restrict__ x,
+                             const ushort_t *__restrict__ wln,
+                             const ushort_t *__restrict__ w,
+                             ushort_t *__restrict__ y, int K, float eps,
+                             RopeKvArgs ra) {
+  extern __shared__ ushort_t xl[];  // K bf16: x*wln (unnormalized)
+  __shared__ float red[16];
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int wid = threadIdx.x / WAVE;
+  const int rg = lane >> 5;
+  const int sl = lane & 31;
+  const int n_even = blockIdx.x * 8 + wid * 2;
+  const int n = n_even + rg;
+
+  // epilogue operands first: their latency hides under prologue + stream
+  const RopeKvPre pre = rope_kv_prefetch(ra, n_even);
+
+  const float rms = norm_stage_lds(x, wln, xl, red, K, eps);
+
+  const ushort_t *wr = w + (size_t)n * K;
+  const int nc = K / 8;
+  float acc = 0.f;
+  int c = sl;
+  for (; c + 224 < nc; c += 256) {
+    bf16x8 wv[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) wv[u] = ((const bf16x8 *)wr)[c + 32 * u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      acc = dot8_bf16(((const bf16x8 *)xl)[c + 32 * u], wv[u], acc);
+  }
+  for (; c < nc; c += 32)
+    acc = dot8_bf16(((const bf16x8 *)xl)[c], ((const bf16x8 *)wr)[c], acc);
+
+#pragma unroll
+  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
+  rope_kv_store(pre, y, n_even, acc * rms, lane);
+}
+
 // 16-lane-group norm variant for LARGE N (lm_head: final_norm fused)
 extern "C" __global__ void __launch_bounds__(256)
 gemv_norm_kernel(const ushort_t *__restrict__ x,
@@ -393,6 +440,18 @@ extern "C" void launch_gemv_norm(const ushort_t *x, const ushort_t *wln,
   else
     gemv_norm_kernel<<<dim3((N + 15) / 16), 256, lds, stream>>>(x, wln, w, y,
                                                                 K, N, eps);
+}
+
+extern "C" void launch_gemv_norm_rope_kv(
+    const ushort_t *x, const ushort_t *wln, const ushort_t *w, ushort_t *y,
+    int K, float eps, const float *cost, const float *sint, ushort_t *kc,
+    ushort_t *vc, const int *page_table, const int *pos_ptr, int pos, int hq,
+    int kh, int hd, int page, hipStream_t stream) {
+  const int N = (hq + 2 * kh) * hd;  // caller checked: hd % 16 == 0, N <= 8192
+  const RopeKvArgs ra = {cost, sint, kc, vc, page_table, pos_ptr,
+                         pos,  hq,   kh, hd, page};
+  gemv_norm_rope_kv_w32_kernel<<<dim3(N / 8), 256, (size_t)K * 2, stream>>>(
+      x, wln, w, y, K, eps, ra);
 }
 
 extern "C" void launch_gemv_res(const ushort_t *x, const ushort_t *w,

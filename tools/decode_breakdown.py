@@ -129,6 +129,25 @@ def main():
     comps["sample+bump"] = bench(lambda: hip.sample_state(
         W.logits.view(-1), tmp_t, tmp_r, tmp_h, tmp_s, tmp_o))
 
+    # the qkv site as the fused decode step launches it: one kernel
+    # (gemv_norm_rope_kv_w32_kernel / gemv_fp8_rope_kv_w32_kernel) for norm +
+    # projection + RoPE + KV append. Not part of the unfused SUM below.
+    if Q is not None:
+        ops.quant_norm_fp8(W.resid, L.attn_norm, W.x8, W.xs, c.norm_eps)
+        fused_name = "gemv_fp8_rope_kv_w32"
+        t_fused = bench(lambda: ops.gemv_fp8_q_rope_kv(
+            W.x8, W.xs, Q["wqkv"].q, Q["wqkv"].s, W.qkv, m.cos, m.sin,
+            cache.k[0], cache.v[0], cache.page_table, 0, h, kh,
+            pos_state=pos)) * nl
+    else:
+        fused_name = "gemv_norm_rope_kv_w32"
+        t_fused = bench(lambda: ops.gemv_norm_rope_kv(
+            W.resid, L.attn_norm, L.wqkv, c.norm_eps, m.cos, m.sin,
+            cache.k[0], cache.v[0], cache.page_table, 0, h, kh,
+            pos_state=pos, out=W.qkv)) * nl
+    print(f"\nfused qkv site ({fused_name}): {t_fused*1e3:.3f} ms/tok vs "
+          f"qkv proj + rope+kv {(comps['qkv proj'] + comps['rope+kv'])*1e3:.3f}")
+
     total = sum(comps.values())
     print(f"\n{'component':16s} {'ms/tok':>9s}  share")
     for k, v in sorted(comps.items(), key=lambda kv: -kv[1]):

@@ -1,4 +1,6 @@
-"""Per-kernel A/B: norm/res-fused decode GEMVs vs their unfused pairs.
+"""Per-kernel A/B: norm/res-fused decode GEMVs vs their unfused pairs, and
+the qkv GEMV with the RoPE + KV-append epilogue
+(gemv_norm_rope_kv_w32_kernel) vs gemv + rmsnorm + rope_kv.
 
 The fusion only pays if fused_kernel <= unfused_gemv + (add_)rmsnorm for
 each site; the first (mixed-stream) cut measured ~0.4 ms/step SLOWER than
@@ -13,6 +15,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 import torch  # noqa: E402
 
 from adversarial_spec_amd import ops  # noqa: E402
+from adversarial_spec_amd.ops import torch_ref  # noqa: E402
 
 DEV = "cuda:0"
 EPS = 1e-5
@@ -56,11 +59,29 @@ def main():
     rn = bench(lambda: ops.rmsnorm(resid, wln, EPS, out=normed))
     arn = bench(lambda: ops.add_rmsnorm(resid, out_d, wln, EPS,
                                         out_resid=r2, out_y=normed))
-    print(f"rmsnorm: {rn:.2f} us   add_rmsnorm: {arn:.2f} us")
+    # rope_kv site: Llama-3-8B heads, the engine's page size, position 8192
+    HQ, KH, HD, PAGE, POS = 32, 8, 128, 256, 8192
+    kc = bf(POS // PAGE + 1, PAGE, KH, HD)
+    vc = bf(POS // PAGE + 1, PAGE, KH, HD)
+    table = torch.arange(kc.shape[0], dtype=torch.int32, device=DEV)
+    cos, sin = torch_ref.rope_tables(HD, POS + PAGE, 500000.0, DEV)
+    pos = torch.tensor([POS], dtype=torch.int32, device=DEV)
+    q_ = qkv[:, : HQ * HD].view(1, HQ, HD)
+    k_ = qkv[:, HQ * HD: (HQ + KH) * HD].view(1, KH, HD)
+    v_ = qkv[:, (HQ + KH) * HD:].view(1, KH, HD)
+    rk = bench(lambda: ops.rope_kv(q_, k_, v_, cos, sin, kc, vc, table, 0,
+                                   pos_state=pos))
+    print(f"rmsnorm: {rn:.2f} us   add_rmsnorm: {arn:.2f} us   "
+          f"rope_kv: {rk:.2f} us")
 
     rows = [
         ("qkv  ", bench(lambda: ops.gemv(normed, w_qkv, out=qkv)),
          bench(lambda: ops.gemv_norm(resid, wln, w_qkv, EPS, out=qkv)), rn),
+        # gemv_norm_rope_kv_w32_kernel vs gemv + rmsnorm + rope_kv
+        ("qkvrope", bench(lambda: ops.gemv(normed, w_qkv, out=qkv)),
+         bench(lambda: ops.gemv_norm_rope_kv(
+             resid, wln, w_qkv, EPS, cos, sin, kc, vc, table, 0, HQ, KH,
+             pos_state=pos, out=qkv)), rn + rk),
         ("gateup", bench(lambda: ops.gemv_gateup(normed, w_gu, act)),
          bench(lambda: ops.gemv_gateup_norm(resid, wln, w_gu, EPS, act)), arn),
         ("o     ", bench(lambda: ops.gemv(x, w_o, out=out_d)),
@@ -70,12 +91,13 @@ def main():
         ("lmhead", bench(lambda: ops.gemv(normed, w_lm, out=logits)),
          bench(lambda: ops.gemv_norm(resid, wln, w_lm, EPS, out=logits)), rn),
     ]
-    print(f"{'site':7s} {'unfused':>9s} {'fused':>9s} {'norm-kern':>10s} "
+    print(f"{'site':7s} {'unfused':>9s} {'fused':>9s} {'side-kern':>10s} "
           f"{'delta/site':>11s}")
     tot = 0.0
     for name, un, fu, nk in rows:
         d = fu - (un + nk)
-        tot += d
+        if name.strip() != "qkv":  # the decode step runs qkvrope at this site
+            tot += d
         print(f"{name:7s} {un:8.2f}u {fu:8.2f}u {nk:9.2f}u {d:+10.2f}u")
     print(f"net per-layer-ish delta (neg = fusion wins): {tot:+.2f} us")
 
