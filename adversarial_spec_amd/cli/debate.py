@@ -133,6 +133,10 @@ Bedrock:
     parser.add_argument("--model-dtype", choices=["bf16", "fp8"], default=None,
                         help="Engine dtype for `local alias` (fp8 = e4m3 "
                              "MFMA prefill + fp8 weight streaming)")
+    parser.add_argument("--kv-dtype", choices=["bf16", "fp8"], default=None,
+                        help="KV-cache storage for `local alias` (fp8 = "
+                             "rowwise e4m3 cache, half the KV bytes; "
+                             "independent of --model-dtype)")
     # misc
     parser.add_argument("--timeout", type=int, default=600,
                         help="Timeout in seconds for model calls (default: 600)")
@@ -226,7 +230,7 @@ def handle_utility_command(args: argparse.Namespace) -> Optional[int]:
     if args.action == "local":
         return providers.handle_local_command(
             args.profile_name, args.bedrock_arg, args.extra_arg,
-            args.weights, args.gpu, args.model_dtype,
+            args.weights, args.gpu, args.model_dtype, args.kv_dtype,
         )
     return None
 

@@ -21,6 +21,7 @@ import torch
 
 from .. import ops
 from ..models import LlamaModel, get_config
+from ..models.llama import KV_DTYPES
 from ..utils.timing import PhaseTimer
 from .tokenizer import build_tokenizer
 
@@ -60,6 +61,19 @@ class _StopScan:
         return _STOP_SUBSTR in self._tok.decode(list(self._ids))
 
 
+def resolve_kv_dtype(spec: dict[str, Any]) -> str:
+    """KV-cache storage format of an engine: the spec key `kv_dtype`
+    ("bf16" | "fp8"); when the key is absent, the environment variable
+    ADVSPEC_KV_DTYPE; otherwise "bf16". Anything else is a ValueError."""
+    kv = spec.get("kv_dtype")
+    if kv is None:
+        kv = os.environ.get("ADVSPEC_KV_DTYPE") or "bf16"
+    if kv not in KV_DTYPES:
+        raise ValueError(
+            f"kv_dtype must be one of {KV_DTYPES}, got {kv!r}")
+    return kv
+
+
 def _seed_from_name(name: str) -> int:
     h = 2166136261
     for ch in name:
@@ -80,6 +94,7 @@ class LocalEngine:
             else:
                 device = "cpu"
         self.device = torch.device(device)
+        self.kv_dtype = resolve_kv_dtype(spec)
         self.model = LlamaModel(
             self.config, device=self.device, seed=_seed_from_name(self.name),
             tp=tp,
@@ -102,6 +117,8 @@ class LocalEngine:
         if spec.get("dtype") == "fp8":
             # BASELINE config 5: e4m3 MFMA prefill + fp8 weight streaming
             self.model.quantize_fp8()
+        # KV-cache storage is its own switch, independent of the weights
+        self.model.kv_dtype = self.kv_dtype
         # ORDER the engine stream after weight init: weights/tables are
         # initialized on the CREATION stream (usually the default stream),
         # but all generate() work runs on self.stream. Without this event
@@ -476,7 +493,8 @@ _ENGINES_LOCK = threading.Lock()
 def get_engine(spec: dict[str, Any], device: Optional[str] = None) -> LocalEngine:
     """Process-wide engine cache: weights stay HBM-resident across rounds."""
     key = (spec.get("name"), spec.get("arch"), spec.get("weights"),
-           spec.get("dtype"), device or spec.get("gpu"))
+           spec.get("dtype"), resolve_kv_dtype(spec),
+           device or spec.get("gpu"))
     with _ENGINES_LOCK:
         eng = _ENGINES.get(key)
         if eng is None:

@@ -62,6 +62,9 @@ class LayerWeights:
     w_down: torch.Tensor  # [d, ffn]
 
 
+KV_DTYPES = ("bf16", "fp8")
+
+
 class PagedKVCache:
     """Block-table KV cache: physical pages of `page_size` tokens.
 
@@ -71,14 +74,31 @@ class PagedKVCache:
     """
 
     def __init__(self, config: LlamaConfig, max_seq: int, device, dtype,
-                 page_size: int = 256) -> None:
+                 page_size: int = 256, kv_dtype: str = "bf16") -> None:
+        if kv_dtype not in KV_DTYPES:
+            raise ValueError(
+                f"kv_dtype must be one of {KV_DTYPES}, got {kv_dtype!r}")
+        self.kv_dtype = kv_dtype
         self.page_size = page_size
         n_pages = (max_seq + page_size - 1) // page_size
         kh, hd = config.n_kv_heads, config.head_dim
         nl = config.n_layers
         # per-layer page pools: [n_layers, n_pages, page_size, kh, hd]
-        self.k = torch.zeros(nl, n_pages, page_size, kh, hd, device=device, dtype=dtype)
-        self.v = torch.zeros(nl, n_pages, page_size, kh, hd, device=device, dtype=dtype)
+        if kv_dtype == "fp8":
+            # opt-in e4m3fn storage (contract in ops/torch_ref.py): 1-byte
+            # elements plus one f32 scale per (position, kv-head) row,
+            # [n_layers, n_pages, kh, page_size] — head-major inside a page
+            # so a decode tile's scales are contiguous.
+            self.k = torch.zeros(nl, n_pages, page_size, kh, hd, device=device,
+                                 dtype=torch.uint8)
+            self.v = torch.zeros_like(self.k)
+            self.k_scale = torch.zeros(nl, n_pages, kh, page_size,
+                                       device=device, dtype=torch.float32)
+            self.v_scale = torch.zeros_like(self.k_scale)
+        else:
+            self.k = torch.zeros(nl, n_pages, page_size, kh, hd, device=device, dtype=dtype)
+            self.v = torch.zeros(nl, n_pages, page_size, kh, hd, device=device, dtype=dtype)
+            self.k_scale = self.v_scale = None
         # identity mapping by default; kept as a real table for paged reads.
         # `identity` certifies page_table[i] == i to the kernels (pure
         # address math, no table read) and to chunked prefill (which views
@@ -174,6 +194,9 @@ class LlamaModel:
         self.lm_head: Optional[torch.Tensor] = None  # [vocab, d]
         self.layers: list[LayerWeights] = []
         self.fp8 = False  # set by quantize_fp8()
+        # storage format of the caches new_cache() hands out; independent
+        # of the weight dtype (the engine sets it from its spec)
+        self.kv_dtype = "bf16"
         # decode-attention split-grid block target; 0 = kernel default
         # (256). The engine sets this from its live-opponent count before
         # capturing decode graphs: solo decode wants ~512 blocks of
@@ -348,9 +371,13 @@ class LlamaModel:
 
     # -- inference ----------------------------------------------------------
 
-    def new_cache(self, max_seq: Optional[int] = None) -> PagedKVCache:
+    def new_cache(self, max_seq: Optional[int] = None,
+                  kv_dtype: Optional[str] = None) -> PagedKVCache:
+        """kv_dtype "bf16" (default: elements in the model dtype) or "fp8"
+        (rowwise e4m3fn, opt-in); None takes the model's `kv_dtype`."""
         return PagedKVCache(
-            self.config, max_seq or self.config.max_seq_len, self.device, self.dtype
+            self.config, max_seq or self.config.max_seq_len, self.device,
+            self.dtype, kv_dtype=kv_dtype or self.kv_dtype,
         )
 
     def _forward(self, tokens: torch.Tensor, cache: PagedKVCache, pos0: int,
@@ -397,12 +424,32 @@ class LlamaModel:
             q = qkv[:, : h * hd].view(t, h, hd)
             k = qkv[:, h * hd : (h + kh) * hd].view(t, kh, hd)
             v = qkv[:, (h + kh) * hd :].view(t, kh, hd)
-            q, k = ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i],
-                               cache.v[i], cache.page_table, pos0,
-                               pos_state=pos_state)
+            kv8 = cache.kv_dtype == "fp8"
+            if kv8:
+                q, k = ops.rope_kv_fp8(
+                    q, k, v, self.cos, self.sin, cache.k[i], cache.v[i],
+                    cache.k_scale[i], cache.v_scale[i], cache.page_table,
+                    pos0, pos_state=pos_state)
+            else:
+                q, k = ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i],
+                                   cache.v[i], cache.page_table, pos0,
+                                   pos_state=pos_state)
             if t > 1:
                 if pos0 == 0:
+                    # (fp8 cache too: single-shot prefill attends over the
+                    # fresh unquantized K/V; only the cache copy is fp8)
                     attn = ops.attn_prefill(q, k, v, self.scale, causal=True)
+                elif kv8:
+                    # chunked prefill over an fp8 cache: the prefix (this
+                    # chunk's own rows included) is read back dequantized,
+                    # so the result is NOT bit-equal to single-shot
+                    # prefill, which never sees quantized K/V.
+                    k_all, v_all = ops.kv_dequant_fp8(
+                        cache.k[i], cache.v[i], cache.k_scale[i],
+                        cache.v_scale[i], cache.page_table, pos0 + t,
+                        dtype=q.dtype)
+                    attn = ops.attn_prefill(q, k_all, v_all, self.scale,
+                                            causal=True, kv_offset=pos0)
                 else:
                     # chunked prefill: this chunk's queries attend to ALL
                     # cached positions plus themselves. The page table is
@@ -416,11 +463,20 @@ class LlamaModel:
                                             causal=True, kv_offset=pos0)
             else:
                 seq = max_seq_bound if pos_state is not None else pos0 + 1
-                attn = ops.attn_decode_paged(
-                    q[0], cache.k[i], cache.v[i], cache.page_table, seq,
-                    self.scale, pos_state=pos_state, identity=cache.identity,
-                    split_blocks=self.split_blocks,
-                ).unsqueeze(0)
+                if kv8:
+                    attn = ops.attn_decode_paged_fp8(
+                        q[0], cache.k[i], cache.v[i], cache.k_scale[i],
+                        cache.v_scale[i], cache.page_table, seq, self.scale,
+                        pos_state=pos_state, identity=cache.identity,
+                        split_blocks=self.split_blocks,
+                    ).unsqueeze(0)
+                else:
+                    attn = ops.attn_decode_paged(
+                        q[0], cache.k[i], cache.v[i], cache.page_table, seq,
+                        self.scale, pos_state=pos_state,
+                        identity=cache.identity,
+                        split_blocks=self.split_blocks,
+                    ).unsqueeze(0)
             attn_out = proj(attn.reshape(t, h * hd), L, Qd, "wo")
             if self.tp is not None and self.tp.size > 1:
                 self.tp.all_reduce_(attn_out)  # row-parallel wo partial sums
@@ -455,7 +511,10 @@ class LlamaModel:
         prefill fits comfortably in 288 GB HBM3E, so chunking is an
         ACTIVATION-memory valve for longer documents, not
         the default. Chunk boundaries re-run attention against the cached
-        prefix (kv_offset), numerically identical to single-shot."""
+        prefix (kv_offset), numerically identical to single-shot — with a
+        bf16 cache. An fp8 cache hands later chunks the DEQUANTIZED prefix,
+        so chunked prefill then agrees with single-shot only to
+        quantization noise, not bitwise."""
         n = tokens.shape[0]
         if n > cache.max_seq:
             raise ValueError(f"prompt {n} exceeds cache {cache.max_seq}")
@@ -539,6 +598,10 @@ class LlamaModel:
         # (every layer's cache is a slice of one tensor: layer 0 speaks for all)
         fuse_rope = ops.qkv_rope_fusable(h, kh, hd, self.cos, self.sin,
                                          cache.k[0], cache.v[0])
+        # an fp8 cache never fuses (qkv_rope_fusable refuses a non-bf16
+        # cache: the per-row amax spans 16 blocks of the w32 GEMV and cannot
+        # ride its epilogue): unfused qkv GEMV, then rope_kv_fp8.
+        kv8 = cache.kv_dtype == "fp8"
         for i, L in enumerate(self.layers):
             Qd = self.layers_q[i] if fp8 else None
             roped = False
@@ -574,14 +637,29 @@ class LlamaModel:
             if not roped:
                 k = W.qkv[:, h * hd : (h + kh) * hd].view(1, kh, hd)
                 v = W.qkv[:, (h + kh) * hd :].view(1, kh, hd)
-                ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i],
-                            cache.v[i], cache.page_table, 0,
-                            pos_state=pos_state)
-            ops.attn_decode_paged(
-                q[0], cache.k[i], cache.v[i], cache.page_table,
-                max_seq_bound, self.scale, pos_state=pos_state, out=W.attn,
-                identity=cache.identity, split_blocks=self.split_blocks,
-            )
+                if kv8:
+                    ops.rope_kv_fp8(q, k, v, self.cos, self.sin, cache.k[i],
+                                    cache.v[i], cache.k_scale[i],
+                                    cache.v_scale[i], cache.page_table, 0,
+                                    pos_state=pos_state)
+                else:
+                    ops.rope_kv(q, k, v, self.cos, self.sin, cache.k[i],
+                                cache.v[i], cache.page_table, 0,
+                                pos_state=pos_state)
+            if kv8:
+                ops.attn_decode_paged_fp8(
+                    q[0], cache.k[i], cache.v[i], cache.k_scale[i],
+                    cache.v_scale[i], cache.page_table, max_seq_bound,
+                    self.scale, pos_state=pos_state, out=W.attn,
+                    identity=cache.identity, split_blocks=self.split_blocks,
+                )
+            else:
+                ops.attn_decode_paged(
+                    q[0], cache.k[i], cache.v[i], cache.page_table,
+                    max_seq_bound, self.scale, pos_state=pos_state,
+                    out=W.attn, identity=cache.identity,
+                    split_blocks=self.split_blocks,
+                )
             if fused_f8:
                 gw = Qd.get("w_gate_up")
                 if _FP8_LDS:

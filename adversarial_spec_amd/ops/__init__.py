@@ -188,6 +188,99 @@ def rope_kv(
     return q2, k2
 
 
+# ---- fp8 (e4m3fn) KV cache (storage contract in torch_ref) -----------------
+
+def rope_kv_fp8(
+    q: torch.Tensor,
+    k: torch.Tensor,
+    v: torch.Tensor,
+    cos: torch.Tensor,
+    sin: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    pos0: int,
+    pos_state: Optional[torch.Tensor] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """fp8 twin of rope_kv: rotates q and k in place (bit-identical to
+    rope_kv) and appends the rotated k and v rowwise-quantized to e4m3fn,
+    one fp32 scale per (position, kv-head) row, in one launch. Returns
+    (q, k) rotated."""
+    if _on_gpu(q):
+        _require_hip().rope_kv_fp8(q, k, v, cos, sin, k_cache, v_cache,
+                                   k_scale, v_scale, page_table, pos0,
+                                   pos_state)
+        return q, k
+    if pos_state is not None:
+        pos0 = int(pos_state.reshape(-1)[0])
+    q2, k2 = torch_ref.rope(q, k, cos, sin, pos0)
+    torch_ref.kv_write_fp8(k_cache, v_cache, k_scale, v_scale, page_table,
+                           pos0, k2, v)
+    return q2, k2
+
+
+def attn_decode_paged_fp8(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    seq_len: int,
+    scale: Optional[float] = None,
+    pos_state: Optional[torch.Tensor] = None,
+    out: Optional[torch.Tensor] = None,
+    identity: bool = False,
+    split_blocks: int = 0,
+) -> torch.Tensor:
+    """attn_decode_paged over an fp8 cache: same arguments plus the two
+    scale tensors; the dequantization is folded into the split kernel (K
+    scale on the score, V scale on p), the combine pass and the split
+    geometry are the bf16 ones."""
+    if _on_gpu(q):
+        import math
+
+        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+        if pos_state is not None:
+            return _require_hip().attn_decode_paged_fp8_ds(
+                q, k_cache, v_cache, k_scale, v_scale, page_table, pos_state,
+                seq_len, s, out, identity, split_blocks,
+            )
+        return _require_hip().attn_decode_paged_fp8(
+            q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len, s,
+            identity, split_blocks)
+    if pos_state is not None:
+        seq_len = int(pos_state.reshape(-1)[0]) + 1
+    return torch_ref.attn_decode_paged_fp8(
+        q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len, scale)
+
+
+def kv_dequant_fp8(
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    n: int,
+    dtype: Optional[torch.dtype] = None,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Positions [0, n) of one layer's fp8 cache as contiguous (k, v)
+    [n, kh, hd], through the page table; bf16 on GPU (bit-exact: exact
+    fp8 -> f32, one fp32 multiply, one rounding), where any other `dtype`
+    is an error; the CPU reference honours `dtype` (default bf16).
+    Chunked prefill only."""
+    if _on_gpu(k_cache):
+        if dtype not in (None, torch.bfloat16):
+            raise ValueError(
+                f"kv_dequant_fp8 returns bf16 on GPU, not {dtype}")
+        return _require_hip().kv_dequant_fp8(k_cache, v_cache, k_scale,
+                                             v_scale, page_table, n)
+    return torch_ref.kv_dequant_fp8(k_cache, v_cache, k_scale, v_scale,
+                                    page_table, n, dtype or torch.bfloat16)
+
+
 def gemv(x: torch.Tensor, w: torch.Tensor,
          out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Batch-1 matmul y = x @ w^T, weights ROW-MAJOR [out, in] (HF layout).

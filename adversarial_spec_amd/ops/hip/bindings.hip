@@ -91,6 +91,18 @@ void launch_gemv_fp8(const uint8_t*, const float*, const uint8_t*, const float*,
                      ushort_t*, int, int, hipStream_t);
 void launch_quant_fp8(const ushort_t*, uint8_t*, float*, int, int, hipStream_t);
 void launch_mfma_rate(const ushort_t*, float*, int, int, hipStream_t);
+void launch_attn_decode_split_fp8(const ushort_t*, const uint8_t*,
+                                  const uint8_t*, const float*, const float*,
+                                  const int*, int, float, int, int, int, int,
+                                  int, int, float*, float*, float*, const int*,
+                                  ushort_t*, int, hipStream_t);
+void launch_rope_kv_fp8(ushort_t*, ushort_t*, const ushort_t*, const float*,
+                        const float*, uint8_t*, uint8_t*, float*, float*,
+                        const int*, int, int, int, int, int, long, long, long,
+                        int, const int*, hipStream_t);
+void launch_kv_dequant_fp8(const uint8_t*, const uint8_t*, const float*,
+                           const float*, const int*, ushort_t*, ushort_t*, int,
+                           int, int, int, hipStream_t);
 }
 
 static hipStream_t cur_stream() {
@@ -974,6 +986,183 @@ void ws_release(torch::Tensor kc_all) {
   }
 }
 
+// --------------------------------------------------------------------------
+// fp8 (e4m3fn) KV cache: kc/vc uint8 [n_pages, page, kh, hd], ksc/vsc f32
+// [n_pages, kh, page] (kv_fp8.hip). The decode entries share split_geometry,
+// the combine kernel and the per-cache workspace map (keyed by the K-cache
+// pointer) with the bf16 ones.
+
+static void check_fp8_cache(const char* who, const torch::Tensor& kc,
+                            const torch::Tensor& vc, const torch::Tensor& ksc,
+                            const torch::Tensor& vsc,
+                            const torch::Tensor& page_table) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && ksc.is_cuda() && vsc.is_cuda() &&
+                  page_table.is_cuda(),
+              who, ": cache, scales and page table must be on GPU");
+  TORCH_CHECK(kc.scalar_type() == at::kByte && vc.scalar_type() == at::kByte,
+              who, ": fp8 cache must be uint8 (e4m3fn bytes)");
+  TORCH_CHECK(ksc.scalar_type() == at::kFloat &&
+                  vsc.scalar_type() == at::kFloat,
+              who, ": cache scales must be f32");
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() &&
+                  kc.sizes() == vc.sizes(),
+              who, ": caches contiguous [n_pages, page, kh, hd], same shape");
+  TORCH_CHECK(ksc.dim() == 3 && ksc.is_contiguous() && vsc.is_contiguous() &&
+                  ksc.sizes() == vsc.sizes() && ksc.size(0) == kc.size(0) &&
+                  ksc.size(1) == kc.size(2) && ksc.size(2) == kc.size(1),
+              who, ": scales contiguous [n_pages, kh, page]");
+  const int64_t hd = kc.size(3);
+  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, who, ": hd in {32, 64, 128}");
+  TORCH_CHECK(page_table.scalar_type() == at::kInt && page_table.dim() == 1 &&
+                  page_table.is_contiguous(),
+              who, ": page_table int32 [n_logical_pages]");
+}
+
+// fp8 twin of rope_kv: rotate q/k in place (bit-identical to rope_kv) and
+// append the rowwise-quantized rotated k and v plus their scales.
+void rope_kv_fp8(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                 torch::Tensor cost, torch::Tensor sint, torch::Tensor kc,
+                 torch::Tensor vc, torch::Tensor ksc, torch::Tensor vsc,
+                 torch::Tensor page_table, int64_t pos0,
+                 const c10::optional<torch::Tensor>& pos_state) {
+  CHECK_BF16_CUDA(q);
+  CHECK_BF16_CUDA(k);
+  CHECK_BF16_CUDA(v);
+  check_fp8_cache("rope_kv_fp8", kc, vc, ksc, vsc, page_table);
+  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3,
+              "rope_kv_fp8: q/k/v [t, heads, hd]");
+  TORCH_CHECK(q.stride(2) == 1 && k.stride(2) == 1 && v.stride(2) == 1,
+              "rope_kv_fp8: dim contiguous");
+  TORCH_CHECK(q.stride(1) == q.size(2) && k.stride(1) == k.size(2) &&
+                  v.stride(1) == v.size(2),
+              "rope_kv_fp8: head dim contiguous");
+  const int t = q.size(0), hq = q.size(1), hd = q.size(2);
+  const int hk = k.size(1);
+  const int page = kc.size(1);
+  TORCH_CHECK(k.size(0) == t && v.size(0) == t && v.size(1) == hk &&
+                  k.size(2) == hd && v.size(2) == hd,
+              "rope_kv_fp8: q/k/v row and head shapes");
+  TORCH_CHECK(kc.size(2) == hk && kc.size(3) == hd,
+              "rope_kv_fp8: cache [.., kh, hd] must match k");
+  TORCH_CHECK(cost.is_cuda() && sint.is_cuda() &&
+                  cost.scalar_type() == at::kFloat &&
+                  sint.scalar_type() == at::kFloat && cost.dim() == 2 &&
+                  cost.is_contiguous() && sint.is_contiguous() &&
+                  cost.sizes() == sint.sizes() && cost.size(1) == hd / 2,
+              "rope_kv_fp8: cos/sin tables f32 contiguous [max_pos, hd/2]");
+  const int* pp = nullptr;
+  if (pos_state.has_value()) {
+    TORCH_CHECK(pos_state->is_cuda() && pos_state->scalar_type() == at::kInt &&
+                    pos_state->numel() >= 1,
+                "rope_kv_fp8: pos_state must be a device int32 word");
+    pp = pos_state->data_ptr<int>();
+  } else {
+    TORCH_CHECK(pos0 >= 0 && pos0 + t <= cost.size(0) &&
+                    pos0 + t <= page_table.numel() * (int64_t)page,
+                "rope_kv_fp8: positions outside the tables");
+  }
+  if (t == 0) return;
+  launch_rope_kv_fp8(uptr_mut(q), uptr_mut(k), uptr(v), cost.data_ptr<float>(),
+                     sint.data_ptr<float>(), kc.data_ptr<uint8_t>(),
+                     vc.data_ptr<uint8_t>(), ksc.data_ptr<float>(),
+                     vsc.data_ptr<float>(), page_table.data_ptr<int>(), t, hq,
+                     hk, hd, (int)pos0, q.stride(0), k.stride(0), v.stride(0),
+                     page, pp, cur_stream());
+}
+
+// Positions [0, n) of one layer's fp8 cache -> contiguous bf16 [n, kh, hd]
+// (k, v), through the page table. Chunked prefill only.
+std::tuple<torch::Tensor, torch::Tensor> kv_dequant_fp8(
+    torch::Tensor kc, torch::Tensor vc, torch::Tensor ksc, torch::Tensor vsc,
+    torch::Tensor page_table, int64_t n) {
+  check_fp8_cache("kv_dequant_fp8", kc, vc, ksc, vsc, page_table);
+  const int page = kc.size(1), kh = kc.size(2), hd = kc.size(3);
+  TORCH_CHECK(n >= 0 && n <= page_table.numel() * (int64_t)page,
+              "kv_dequant_fp8: n outside the page table");
+  auto opts = torch::TensorOptions().dtype(at::kBFloat16).device(kc.device());
+  auto kout = torch::empty({n, kh, hd}, opts);
+  auto vout = torch::empty({n, kh, hd}, opts);
+  launch_kv_dequant_fp8(kc.data_ptr<uint8_t>(), vc.data_ptr<uint8_t>(),
+                        ksc.data_ptr<float>(), vsc.data_ptr<float>(),
+                        page_table.data_ptr<int>(), uptr_mut(kout),
+                        uptr_mut(vout), (int)n, kh, hd, page, cur_stream());
+  return {kout, vout};
+}
+
+// Shared body of the two fp8 decode entries. `bound` sizes the split
+// geometry (host length, or max_seq in graph mode where the true length is
+// *pos_state + 1 in-kernel).
+static torch::Tensor attn_decode_fp8_impl(
+    const char* who, torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
+    torch::Tensor ksc, torch::Tensor vsc, torch::Tensor page_table,
+    int64_t bound, double scale, const int* pos_ptr,
+    c10::optional<torch::Tensor> out_opt, bool identity,
+    int64_t split_blocks) {
+  CHECK_BF16_CUDA(q);
+  check_fp8_cache(who, kc, vc, ksc, vsc, page_table);
+  TORCH_CHECK(q.dim() == 2, who, ": q [hq, hd]");
+  auto qc = q.contiguous();
+  const int hq = qc.size(0), hd = qc.size(1);
+  const int page = kc.size(1), kh = kc.size(2);
+  TORCH_CHECK(kc.size(3) == hd, who, ": q and cache head dims differ");
+  TORCH_CHECK(hq % kh == 0 && hq / kh <= 8, who, ": GQA group <= 8");
+  const int group = hq / kh;
+  const int64_t covered =
+      (identity ? kc.size(0) : page_table.numel()) * (int64_t)page;
+  TORCH_CHECK(bound >= 1 && bound <= covered, who,
+              ": seq_len outside the cache");
+  int n_splits, split_len;
+  split_geometry(bound, kh, (int)split_blocks, &n_splits, &split_len);
+  torch::Tensor out;
+  if (out_opt.has_value()) {
+    out = *out_opt;
+    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 &&
+                    out.is_contiguous() && out.numel() == (int64_t)hq * hd,
+                who, ": out must be contiguous bf16 [hq, hd]");
+  } else {
+    out = torch::empty({hq, hd}, qc.options());
+  }
+  const long khnsg = (long)kh * n_splits * group;
+  float* ws;
+  {
+    std::lock_guard<std::mutex> lk(g_ws_mu);
+    auto& w = g_ws[(void*)kc.data_ptr()];
+    ws = ws_f32(w.attn_ws, w.retired, khnsg * (2 + hd), q.device());
+  }
+  launch_attn_decode_split_fp8(
+      uptr(qc), kc.data_ptr<uint8_t>(), vc.data_ptr<uint8_t>(),
+      ksc.data_ptr<float>(), vsc.data_ptr<float>(), page_table.data_ptr<int>(),
+      (int)bound, (float)scale, kh, group, hd, page, split_len, n_splits, ws,
+      ws + khnsg, ws + 2 * khnsg, pos_ptr, uptr_mut(out), identity ? 1 : 0,
+      cur_stream());
+  return out;
+}
+
+torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kc,
+                                    torch::Tensor vc, torch::Tensor ksc,
+                                    torch::Tensor vsc,
+                                    torch::Tensor page_table, int64_t seq_len,
+                                    double scale, bool identity,
+                                    int64_t split_blocks) {
+  return attn_decode_fp8_impl("attn_decode_paged_fp8", q, kc, vc, ksc, vsc,
+                              page_table, seq_len, scale, nullptr,
+                              c10::nullopt, identity, split_blocks);
+}
+
+torch::Tensor attn_decode_paged_fp8_ds(
+    torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor ksc,
+    torch::Tensor vsc, torch::Tensor page_table, torch::Tensor pos_state,
+    int64_t max_seq, double scale, c10::optional<torch::Tensor> out_opt,
+    bool identity, int64_t split_blocks) {
+  TORCH_CHECK(pos_state.is_cuda() && pos_state.scalar_type() == at::kInt &&
+                  pos_state.numel() >= 1,
+              "attn_decode_paged_fp8_ds: pos_state must be a device int32 word");
+  return attn_decode_fp8_impl("attn_decode_paged_fp8_ds", q, kc, vc, ksc, vsc,
+                              page_table, max_seq, scale,
+                              pos_state.data_ptr<int>(), out_opt, identity,
+                              split_blocks);
+}
+
 void bump(torch::Tensor pos_state, torch::Tensor step_state) {
   bump_kernel<<<1, 64, 0, cur_stream()>>>(pos_state.data_ptr<int>(),
                                           step_state.data_ptr<int>());
@@ -1058,6 +1247,28 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("split_blocks") = 0);
   m.def("sample_state", &sample_state, "graph-mode on-device sampling");
   m.def("bump", &bump, "graph-mode pos/step bump");
+  m.def("rope_kv_fp8", &rope_kv_fp8,
+        "fused RoPE + rowwise-e4m3 quantizing paged KV append",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cost"),
+        py::arg("sint"), py::arg("kc"), py::arg("vc"), py::arg("ksc"),
+        py::arg("vsc"), py::arg("page_table"), py::arg("pos0"),
+        py::arg("pos_state") = py::none());
+  m.def("kv_dequant_fp8", &kv_dequant_fp8,
+        "fp8 KV cache positions [0, n) -> contiguous bf16 (k, v)",
+        py::arg("kc"), py::arg("vc"), py::arg("ksc"), py::arg("vsc"),
+        py::arg("page_table"), py::arg("n"));
+  m.def("attn_decode_paged_fp8", &attn_decode_paged_fp8,
+        "paged decode attention over an fp8 KV cache",
+        py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("ksc"),
+        py::arg("vsc"), py::arg("page_table"), py::arg("seq_len"),
+        py::arg("scale"), py::arg("identity") = false,
+        py::arg("split_blocks") = 0);
+  m.def("attn_decode_paged_fp8_ds", &attn_decode_paged_fp8_ds,
+        "graph-mode paged decode attention over an fp8 KV cache",
+        py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("ksc"),
+        py::arg("vsc"), py::arg("page_table"), py::arg("pos_state"),
+        py::arg("max_seq"), py::arg("scale"), py::arg("out") = py::none(),
+        py::arg("identity") = false, py::arg("split_blocks") = 0);
   m.def("ws_release", &ws_release,
         "drop decode-attention scratch for a dead KV cache");
 }

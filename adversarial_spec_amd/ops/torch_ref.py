@@ -171,6 +171,107 @@ def kv_write(
     v_cache.view(npg * ps, kh, hd)[flat] = v.to(v_cache.dtype)
 
 
+# ---- fp8 (e4m3fn) KV cache -------------------------------------------------
+# Storage contract (shared with ops/hip/kv_fp8.hip):
+#   k_cache, v_cache  uint8 [n_pages, page, kh, hd], OCP e4m3fn bytes
+#   k_scale, v_scale  f32   [n_pages, kh, page] (head-major inside a page)
+# One scale per (position, kv-head) row of hd elements:
+#   scale = max(amax|x|, 1e-12) / 448 in fp32;  q = e4m3fn_rne(x / scale)
+# — the rule of ops.quantize_fp8_rowwise, with a quantized zero always
+# stored as byte 0x00. K is quantized after RoPE.
+
+def quantize_kv_fp8(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """x [..., hd] -> (uint8 [..., hd], f32 scale [...]), one scale per row."""
+    xf = x.float()
+    scale = xf.abs().amax(dim=-1).clamp_min(1e-12) / 448.0
+    q = (xf / scale.unsqueeze(-1)).to(torch.float8_e4m3fn).view(torch.uint8)
+    # a quantized zero is always byte 0x00 (never -0 = 0x80): an all-zero
+    # row is all zero bytes even where RoPE left -0.0 in it
+    q = torch.where((q & 0x7F) == 0, torch.zeros_like(q), q)
+    return q.contiguous(), scale.contiguous()
+
+
+def dequantize_kv_fp8(q: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Inverse of quantize_kv_fp8 in fp32: exact fp8 -> f32, one multiply."""
+    return q.view(torch.float8_e4m3fn).float() * scale.unsqueeze(-1)
+
+
+def kv_write_fp8(
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    pos0: int,
+    k: torch.Tensor,
+    v: torch.Tensor,
+) -> None:
+    """Quantize t new K/V rows [t, kh, hd] and scatter bytes and scales into
+    the paged fp8 cache at positions pos0..pos0+t-1."""
+    npg, ps, kh, hd = k_cache.shape
+    t = k.shape[0]
+    pos = torch.arange(pos0, pos0 + t, device=k.device)
+    pages = page_table[(pos // ps).long()].long()
+    inpage = pos % ps
+    flat = pages * ps + inpage
+    for cache, sc, x in ((k_cache, k_scale, k), (v_cache, v_scale, v)):
+        q8, s = quantize_kv_fp8(x)
+        cache.view(npg * ps, kh, hd)[flat] = q8
+        sc[pages, :, inpage] = s
+
+
+def dequant_cache_fp8(cache: torch.Tensor, scale: torch.Tensor) -> torch.Tensor:
+    """Whole fp8 page pool -> fp32 [n_pages, page, kh, hd]."""
+    return dequantize_kv_fp8(cache, scale.permute(0, 2, 1))
+
+
+def kv_dequant_fp8(
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    n: int,
+    dtype: torch.dtype = torch.bfloat16,
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Positions [0, n) of an fp8 cache as contiguous [n, kh, hd] tensors of
+    `dtype`, through the page table: one fp32 multiply, one rounding."""
+    npg, ps, kh, hd = k_cache.shape
+    n_used = (n + ps - 1) // ps
+    phys = page_table[:n_used].long()
+    outs = []
+    for cache, sc in ((k_cache, k_scale), (v_cache, v_scale)):
+        full = dequant_cache_fp8(cache[phys], sc[phys])
+        outs.append(full.reshape(n_used * ps, kh, hd)[:n].to(dtype).contiguous())
+    return outs[0], outs[1]
+
+
+def attn_decode_paged_fp8(
+    q: torch.Tensor,
+    k_cache: torch.Tensor,
+    v_cache: torch.Tensor,
+    k_scale: torch.Tensor,
+    v_scale: torch.Tensor,
+    page_table: torch.Tensor,
+    seq_len: int,
+    scale: Optional[float] = None,
+) -> torch.Tensor:
+    """attn_decode_paged over the dequantized (fp32) positions [0, seq_len)
+    of an fp8 cache; nothing at or past seq_len is read."""
+    ps = k_cache.shape[1]
+    n_used = (seq_len + ps - 1) // ps
+    k, v = kv_dequant_fp8(k_cache, v_cache, k_scale, v_scale, page_table,
+                          seq_len, torch.float32)
+    pad = n_used * ps - seq_len
+    if pad:
+        k = torch.cat([k, k.new_zeros(pad, *k.shape[1:])])
+        v = torch.cat([v, v.new_zeros(pad, *v.shape[1:])])
+    ident = torch.arange(n_used, dtype=page_table.dtype, device=q.device)
+    return attn_decode_paged(
+        q, k.view(n_used, ps, *k.shape[1:]), v.view(n_used, ps, *v.shape[1:]),
+        ident, seq_len, scale)
+
+
 def sample(
     logits: torch.Tensor,
     temperature: float = 0.7,

@@ -510,7 +510,8 @@ def handle_bedrock_command(subcommand: Optional[str], arg: Optional[str],
 def handle_local_command(subcommand: Optional[str], arg: Optional[str],
                          extra: Optional[str], weights: Optional[str],
                          gpu: Optional[int],
-                         dtype: Optional[str] = None) -> int:
+                         dtype: Optional[str] = None,
+                         kv_dtype: Optional[str] = None) -> int:
     """`debate.py local {status,add-model,remove-model,alias,list-models}` —
     manages the MI355X model registry section of the global config."""
     config = load_global_config()
@@ -567,6 +568,8 @@ def handle_local_command(subcommand: Optional[str], arg: Optional[str],
             spec["gpu"] = gpu
         if dtype:
             spec["dtype"] = dtype
+        if kv_dtype:
+            spec["kv_dtype"] = kv_dtype
         local.setdefault("custom_aliases", {})[arg] = spec
         save_global_config(config)
         print(f"Local alias added: {arg} -> {json.dumps(spec)}")

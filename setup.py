@@ -24,6 +24,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "elementwise.hip"),
         os.path.join(HIP_DIR, "attention.hip"),
         os.path.join(HIP_DIR, "attn_prefill_mfma.hip"),
+        os.path.join(HIP_DIR, "kv_fp8.hip"),
         os.path.join(HIP_DIR, "gemv.hip"),
         os.path.join(HIP_DIR, "gemm.hip"),
         os.path.join(HIP_DIR, "gemm256.hip"),

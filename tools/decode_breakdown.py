@@ -33,6 +33,10 @@ def main():
     spec = {"name": "probe", "arch": "llama-3-8b"}
     if dtype == "fp8":
         spec["dtype"] = "fp8"
+    # optional second argument: KV-cache storage (bf16 | fp8); absent, the
+    # engine's own default (ADVSPEC_KV_DTYPE, else bf16) applies
+    if len(sys.argv) > 2:
+        spec["kv_dtype"] = sys.argv[2]
     eng = LocalEngine(spec, device="cuda:0")
     m = eng.model
     c = m.config
@@ -66,7 +70,11 @@ def main():
     with torch.cuda.graph(g, stream=s):
         m.decode_step_ws(cache, pos, max_seq, W)
     t_graph = bench(lambda: g.replay(), iters=100)
-    print(f"decode step graph replay: {t_graph*1e3:.3f} ms/tok")
+    print(f"decode step graph replay: {t_graph*1e3:.3f} ms/tok "
+          f"(weights {dtype}, kv {cache.kv_dtype})")
+    if cache.kv_dtype != "bf16":
+        # the component table below times the bf16-cache kernels
+        return
 
     # ---- component sums over 32 layers ----
     L = m.layers[0]
