@@ -11,6 +11,7 @@ CPU tensors use the fp32 reference in `torch_ref` (tests, BASELINE config 1).
 
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional, Tuple
 
@@ -55,6 +56,11 @@ def _on_gpu(x: torch.Tensor) -> bool:
     return x.is_cuda
 
 
+def _attn_scale(q: torch.Tensor, scale: Optional[float]) -> float:
+    """The softmax scale the kernels take: 1/sqrt(hd) unless given."""
+    return scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+
+
 # --------------------------------------------------------------------------
 # Public ops. Shapes documented in torch_ref (the contract is identical).
 # --------------------------------------------------------------------------
@@ -81,10 +87,7 @@ def rope(
     pos_state: Optional[torch.Tensor] = None,
 ) -> Tuple[torch.Tensor, torch.Tensor]:
     if _on_gpu(q):
-        if pos_state is not None:
-            _require_hip().rope_inplace_ds(q, k, cos, sin, pos_state)
-        else:
-            _require_hip().rope_inplace(q, k, cos, sin, pos0)
+        _require_hip().rope_inplace(q, k, cos, sin, pos0, pos_state)
         return q, k
     return torch_ref.rope(q, k, cos, sin, pos0)
 
@@ -105,10 +108,8 @@ def attn_prefill(
     kv_offset: int = 0,
 ) -> torch.Tensor:
     if _on_gpu(q):
-        import math
-
-        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        return _require_hip().attn_prefill(q, k, v, s, causal, kv_offset)
+        return _require_hip().attn_prefill(q, k, v, _attn_scale(q, scale),
+                                           causal, kv_offset)
     return torch_ref.attn_prefill(q, k, v, scale, causal, kv_offset)
 
 
@@ -128,21 +129,13 @@ def attn_decode_paged(
     cache): the split kernel then does pure address math — the per-lane
     table read otherwise forces a DMA-queue drain per staged tile.
     split_blocks>0 sets the split-grid block target (the engine passes its
-    concurrency-aware pick; ADVSPEC_SPLIT_BLOCKS still overrides)."""
+    concurrency-aware pick; ADVSPEC_SPLIT_BLOCKS still overrides).
+    With pos_state (graph mode) the true length is *pos_state + 1 in-kernel
+    and seq_len is the static max bound sizing the split geometry."""
     if _on_gpu(q):
-        import math
-
-        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        if pos_state is not None:
-            # graph mode: true length = *pos_state + 1 in-kernel; seq_len is
-            # the static max bound sizing the split geometry.
-            return _require_hip().attn_decode_paged_ds(
-                q, k_cache, v_cache, page_table, pos_state, seq_len, s,
-                out, identity, split_blocks,
-            )
         return _require_hip().attn_decode_paged(
-            q, k_cache, v_cache, page_table, seq_len, s, identity,
-            split_blocks)
+            q, k_cache, v_cache, page_table, seq_len, _attn_scale(q, scale),
+            pos_state, out, identity, split_blocks)
     return torch_ref.attn_decode_paged(q, k_cache, v_cache, page_table, seq_len, scale)
 
 
@@ -156,10 +149,8 @@ def kv_write(
     pos_state: Optional[torch.Tensor] = None,
 ) -> None:
     if _on_gpu(k_cache):
-        if pos_state is not None:
-            _require_hip().kv_write_ds(k_cache, v_cache, page_table, pos_state, k, v)
-        else:
-            _require_hip().kv_write(k_cache, v_cache, page_table, pos0, k, v)
+        _require_hip().kv_write(k_cache, v_cache, page_table, pos0, k, v,
+                                pos_state)
         return
     torch_ref.kv_write(k_cache, v_cache, page_table, pos0, k, v)
 
@@ -240,17 +231,9 @@ def attn_decode_paged_fp8(
     scale on the score, V scale on p), the combine pass and the split
     geometry are the bf16 ones."""
     if _on_gpu(q):
-        import math
-
-        s = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
-        if pos_state is not None:
-            return _require_hip().attn_decode_paged_fp8_ds(
-                q, k_cache, v_cache, k_scale, v_scale, page_table, pos_state,
-                seq_len, s, out, identity, split_blocks,
-            )
         return _require_hip().attn_decode_paged_fp8(
-            q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len, s,
-            identity, split_blocks)
+            q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len,
+            _attn_scale(q, scale), pos_state, out, identity, split_blocks)
     if pos_state is not None:
         seq_len = int(pos_state.reshape(-1)[0]) + 1
     return torch_ref.attn_decode_paged_fp8(

@@ -19,6 +19,7 @@
 // State is fp32 throughout; hd in {32, 64, 128}; group = hq/kh <= 8.
 
 #include "common.h"
+#include "launchers.h"
 
 #define MAXG 8
 
@@ -510,46 +511,56 @@ __global__ void __launch_bounds__(256) attn_prefill_simple_kernel(
 // C-linkage launch wrappers (templated LPP dispatch)
 // ---------------------------------------------------------------------------
 
-extern "C" void launch_attn_decode_split(
-    const ushort_t *q, const ushort_t *kc, const ushort_t *vc,
-    const int *page_table, int seq_len, float scale, int kh, int group,
-    int hd, int page, int split_len, int n_splits, float *ws_m, float *ws_l,
-    float *ws_acc, const int *pos_ptr, ushort_t *out, int identity,
-    hipStream_t stream) {
-  dim3 grid(kh, n_splits);
+// One block per (q head, 64-wide slice of hd); the only place this grid rule
+// is written: the bf16 split launcher below and the fp8 one (kv_fp8.hip)
+// both come through here.
+extern "C" void launch_attn_decode_combine(const float *ws_m,
+                                           const float *ws_l,
+                                           const float *ws_acc, ushort_t *out,
+                                           int n_splits, int kh, int group,
+                                           int hd, hipStream_t stream) {
+  attn_decode_combine_kernel<<<dim3(kh * group, (hd + 63) / 64), 256, 0,
+                               stream>>>(ws_m, ws_l, ws_acc, out, n_splits,
+                                         group, hd);
+}
+
+extern "C" void launch_attn_decode_split(const ushort_t *q, const ushort_t *kc,
+                                         const ushort_t *vc,
+                                         const DecodeSplitArgs &a,
+                                         ushort_t *out, hipStream_t stream) {
+  dim3 grid(a.kh, a.n_splits);
   const int lds = 0;  // all LDS is static in the kernel (stage + merge)
   // MG = smallest supported bound >= group keeps the per-head state arrays
   // (q fragments + online-softmax accumulators) sized to the real GQA
   // group; IDENT elides the page-table read (identity single-pool cache).
 #define DISPATCH_ONE(LPP, MG)                                                  \
   do {                                                                         \
-    if (identity)                                                              \
+    if (a.identity)                                                            \
       attn_decode_split_kernel<LPP, MG, true><<<grid, 256, lds, stream>>>(     \
-          q, kc, vc, page_table, seq_len, scale, kh, group, hd, page,          \
-          split_len, ws_m, ws_l, ws_acc, pos_ptr, out);                        \
+          q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,    \
+          a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);      \
     else                                                                       \
       attn_decode_split_kernel<LPP, MG, false><<<grid, 256, lds, stream>>>(    \
-          q, kc, vc, page_table, seq_len, scale, kh, group, hd, page,          \
-          split_len, ws_m, ws_l, ws_acc, pos_ptr, out);                        \
+          q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,    \
+          a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);      \
   } while (0)
 #define DISPATCH_MG(LPP)                                                       \
   do {                                                                         \
-    if (group <= 2) DISPATCH_ONE(LPP, 2);                                      \
-    else if (group <= 4) DISPATCH_ONE(LPP, 4);                                 \
+    if (a.group <= 2) DISPATCH_ONE(LPP, 2);                                    \
+    else if (a.group <= 4) DISPATCH_ONE(LPP, 4);                               \
     else DISPATCH_ONE(LPP, 8);                                                 \
   } while (0)
 
-  switch (hd / 8) {
+  switch (a.hd / 8) {
     case 4: DISPATCH_MG(4); break;
     case 8: DISPATCH_MG(8); break;
     case 16: DISPATCH_MG(16); break;
   }
 #undef DISPATCH_MG
 #undef DISPATCH_ONE
-  if (n_splits > 1) {
-    attn_decode_combine_kernel<<<dim3(kh * group, (hd + 63) / 64), 256, 0,
-                                 stream>>>(ws_m, ws_l, ws_acc, out, n_splits,
-                                           group, hd);
+  if (a.n_splits > 1) {
+    launch_attn_decode_combine(a.ws_m, a.ws_l, a.ws_acc, out, a.n_splits,
+                               a.kh, a.group, a.hd, stream);
   }
 }
 

@@ -24,6 +24,7 @@
 //     C/D: lane l, reg r holds C[row = (l>>4)*4 + r][col = l&15]
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8v;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;
@@ -381,4 +382,9 @@ mfma_probe_16x16x32(const ushort_t *__restrict__ a,  // [16][32]
   c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af, bf, c, 0, 0, 0);
 #pragma unroll
   for (int r = 0; r < 4; ++r) d[(lhi * 4 + r) * 16 + lrow] = c[r];
+}
+
+extern "C" void launch_mfma_probe16(const ushort_t *a, const ushort_t *b,
+                                    float *d, hipStream_t stream) {
+  mfma_probe_16x16x32<<<1, 64, 0, stream>>>(a, b, d);  // one wave, one MFMA
 }

@@ -12,98 +12,7 @@
 #include <unordered_map>
 #include <vector>
 
-using ushort_t = unsigned short;
-
-// launch wrappers defined in the .hip translation units
-extern "C" {
-void launch_attn_decode_split(const ushort_t*, const ushort_t*, const ushort_t*,
-                              const int*, int, float, int, int, int, int, int,
-                              int, float*, float*, float*, const int*,
-                              ushort_t*, int, hipStream_t);
-void launch_attn_prefill_simple(const ushort_t*, const ushort_t*, const ushort_t*,
-                                ushort_t*, int, int, int, float, int, int, int,
-                                int, hipStream_t);
-void launch_attn_prefill_mfma(const ushort_t*, const ushort_t*, const ushort_t*,
-                              ushort_t*, int, int, int, float, int, int, int,
-                              hipStream_t, int* ok);
-void launch_attn_prefill_mfma_abl(const ushort_t*, const ushort_t*,
-                                  const ushort_t*, ushort_t*, int, int, float,
-                                  int, int, int, hipStream_t);
-__global__ void mfma_probe_16x16x32(const ushort_t*, const ushort_t*, float*);
-__global__ void rmsnorm_kernel(const ushort_t*, const ushort_t*, ushort_t*, int, float);
-__global__ void add_rmsnorm_kernel(const ushort_t*, const ushort_t*, const ushort_t*,
-                                   ushort_t*, ushort_t*, int, float);
-__global__ void rope_kernel(ushort_t*, ushort_t*, const float*, const float*,
-                            int, int, int, int, int, long, long, const int*);
-__global__ void swiglu_kernel(const ushort_t*, const ushort_t*, ushort_t*, int, int, int);
-__global__ void kv_write_kernel(const ushort_t*, const ushort_t*, ushort_t*, ushort_t*,
-                                const int*, int, int, int, int, int, const int*);
-__global__ void rope_kv_kernel(ushort_t*, ushort_t*, const ushort_t*,
-                               const float*, const float*, ushort_t*, ushort_t*,
-                               const int*, int, int, int, int, int, long, long,
-                               long, int, const int*);
-__global__ void sample_kernel(const ushort_t*, int, float, uint32_t, int*);
-__global__ void sample_state_kernel(const ushort_t*, int, const float*,
-                                    uint32_t*, int*, const int*, long long*);
-__global__ void bump_kernel(int*, int*);
-void launch_gemv(const ushort_t*, const ushort_t*, ushort_t*, int, int,
-                 hipStream_t);
-void launch_gemv_gateup(const ushort_t*, const ushort_t*, ushort_t*, int, int,
-                        hipStream_t);
-void launch_gemv_norm(const ushort_t*, const ushort_t*, const ushort_t*,
-                      ushort_t*, int, int, float, hipStream_t);
-void launch_gemv_norm_rope_kv(const ushort_t*, const ushort_t*,
-                              const ushort_t*, ushort_t*, int, float,
-                              const float*, const float*, ushort_t*, ushort_t*,
-                              const int*, const int*, int, int, int, int, int,
-                              hipStream_t);
-void launch_gemv_fp8_rope_kv(const uint8_t*, const float*, const uint8_t*,
-                             const float*, ushort_t*, int, const float*,
-                             const float*, ushort_t*, ushort_t*, const int*,
-                             const int*, int, int, int, int, int, hipStream_t);
-void launch_gemv_res(const ushort_t*, const ushort_t*, ushort_t*, int, int,
-                     hipStream_t);
-void launch_gemv_gateup_norm(const ushort_t*, const ushort_t*, const ushort_t*,
-                             ushort_t*, int, int, float, hipStream_t);
-void launch_gemm(const ushort_t*, const ushort_t*, ushort_t*, int, int, int,
-                 hipStream_t);
-void launch_gemm256(const ushort_t*, const ushort_t*, ushort_t*, int, int, int,
-                    hipStream_t);
-void launch_gemm_fp8(const uint8_t*, const float*, const uint8_t*, const float*,
-                     ushort_t*, int, int, int, hipStream_t);
-void launch_gemm_fp8_256(const uint8_t*, const float*, const uint8_t*,
-                         const float*, ushort_t*, int, int, int, hipStream_t);
-void launch_quant_norm_fp8(const ushort_t*, const ushort_t*, uint8_t*, float*,
-                           int, float, hipStream_t);
-void launch_gemv_fp8_norm(const ushort_t*, const ushort_t*, const uint8_t*,
-                          const float*, ushort_t*, int, int, float,
-                          hipStream_t);
-void launch_gemv_fp8_resl(const ushort_t*, const uint8_t*, const float*,
-                          ushort_t*, int, int, hipStream_t);
-void launch_gemv_fp8_gateup_norm(const ushort_t*, const ushort_t*,
-                                 const uint8_t*, const float*, ushort_t*,
-                                 int, int, float, hipStream_t);
-void launch_gemv_fp8_res(const uint8_t*, const float*, const uint8_t*,
-                         const float*, ushort_t*, int, int, hipStream_t);
-void launch_gemv_fp8_gateup(const uint8_t*, const float*, const uint8_t*,
-                            const float*, ushort_t*, int, int, hipStream_t);
-void launch_gemv_fp8(const uint8_t*, const float*, const uint8_t*, const float*,
-                     ushort_t*, int, int, hipStream_t);
-void launch_quant_fp8(const ushort_t*, uint8_t*, float*, int, int, hipStream_t);
-void launch_mfma_rate(const ushort_t*, float*, int, int, hipStream_t);
-void launch_attn_decode_split_fp8(const ushort_t*, const uint8_t*,
-                                  const uint8_t*, const float*, const float*,
-                                  const int*, int, float, int, int, int, int,
-                                  int, int, float*, float*, float*, const int*,
-                                  ushort_t*, int, hipStream_t);
-void launch_rope_kv_fp8(ushort_t*, ushort_t*, const ushort_t*, const float*,
-                        const float*, uint8_t*, uint8_t*, float*, float*,
-                        const int*, int, int, int, int, int, long, long, long,
-                        int, const int*, hipStream_t);
-void launch_kv_dequant_fp8(const uint8_t*, const uint8_t*, const float*,
-                           const float*, const int*, ushort_t*, ushort_t*, int,
-                           int, int, int, hipStream_t);
-}
+#include "launchers.h"
 
 static hipStream_t cur_stream() {
   return c10::hip::getCurrentHIPStream().stream();
@@ -118,21 +27,27 @@ static hipStream_t cur_stream() {
 // engines the same underlying stream. Grown buffers retire the old tensor
 // into a keep-alive list because a previously captured graph may still
 // replay with the old pointer.
-struct StreamWS {
+struct CacheWS {
   torch::Tensor attn_ws;   // fp32 scratch: decode-attention m/l/acc
   std::vector<torch::Tensor> retired;
 };
 static std::mutex g_ws_mu;
-static std::unordered_map<void*, StreamWS> g_ws;
+static std::unordered_map<void*, CacheWS> g_ws;
 
-static float* ws_f32(torch::Tensor& t, std::vector<torch::Tensor>& retired,
-                     int64_t elems, const torch::Device& dev) {
-  if (!t.defined() || t.numel() < elems) {
-    if (t.defined()) retired.push_back(t);
-    t = torch::empty({std::max<int64_t>(elems, 64)},
+// The m | l | acc scratch of a decode call on cache `kc`: khnsg * (2 + hd)
+// floats (khnsg = kh * n_splits * group), grown on demand.
+static float* decode_workspace(const torch::Tensor& kc, int64_t khnsg, int hd,
+                               const torch::Device& dev) {
+  const int64_t elems = khnsg * (2 + hd);
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  CacheWS& w = g_ws[kc.data_ptr()];
+  if (!w.attn_ws.defined() || w.attn_ws.numel() < elems) {
+    if (w.attn_ws.defined()) w.retired.push_back(w.attn_ws);
+    w.attn_ws =
+        torch::empty({std::max<int64_t>(elems, 64)},
                      torch::TensorOptions().dtype(at::kFloat).device(dev));
   }
-  return t.data_ptr<float>();
+  return w.attn_ws.data_ptr<float>();
 }
 
 #define CHECK_BF16_CUDA(t)                                                 \
@@ -147,9 +62,121 @@ static ushort_t* uptr_mut(torch::Tensor& t) {
 }
 
 // --------------------------------------------------------------------------
+// Argument checkers shared by every op that takes these tensors, host-
+// position and graph-mode (pos_state) calls alike. Tensor metadata only:
+// nothing here reads the device, synchronizes, allocates or launches, so
+// nothing is added to a captured graph.
+
+using OptTensor = c10::optional<torch::Tensor>;
+
+// Graph mode keeps the position in a device int32 word; returns its address,
+// or nullptr for a host-position call.
+static const int* check_pos_state(const char* who, const OptTensor& pos_state) {
+  if (!pos_state.has_value()) return nullptr;
+  TORCH_CHECK(pos_state->is_cuda() && pos_state->scalar_type() == at::kInt &&
+                  pos_state->numel() >= 1,
+              who, ": pos_state must be a device int32 word");
+  return pos_state->data_ptr<int>();
+}
+
+// A host position range [pos0, pos0 + t) must lie inside the cos/sin tables
+// (when given) and inside what the page table maps. A device position is
+// trusted: checking it would mean reading it.
+static void check_host_pos(const char* who, int64_t pos0, int64_t t,
+                           const torch::Tensor* cost,
+                           const torch::Tensor* page_table, int64_t page) {
+  TORCH_CHECK(pos0 >= 0 && (!cost || pos0 + t <= cost->size(0)) &&
+                  (!page_table || pos0 + t <= page_table->numel() * page),
+              who, ": pos inside the rope table and the page table");
+}
+
+static void check_rope_tables(const char* who, const torch::Tensor& cost,
+                              const torch::Tensor& sint, int hd) {
+  TORCH_CHECK(cost.is_cuda() && sint.is_cuda() &&
+                  cost.scalar_type() == at::kFloat &&
+                  sint.scalar_type() == at::kFloat,
+              who, ": cos/sin tables f32 on GPU");
+  TORCH_CHECK(cost.dim() == 2 && cost.is_contiguous() &&
+                  sint.is_contiguous() && cost.sizes() == sint.sizes() &&
+                  cost.size(1) == hd / 2,
+              who, ": cos/sin tables [max_pos, hd/2] contiguous");
+}
+
+// q [t, hq, hd], k [t, hk, hd] and (when given) v [t, hk, hd]: bf16, possibly
+// strided VIEWS of the fused QKV output — an arbitrary row stride, but
+// contiguous head and dim dims.
+static void check_qkv_views(const char* who, const torch::Tensor& q,
+                            const torch::Tensor& k, const torch::Tensor* v) {
+  for (const torch::Tensor* x : {&q, &k, v}) {
+    if (!x) continue;
+    TORCH_CHECK(x->is_cuda() && x->scalar_type() == at::kBFloat16 &&
+                    x->dim() == 3,
+                who, ": q/k/v bf16 [t, heads, hd] on GPU");
+    TORCH_CHECK(x->stride(2) == 1, who, ": dim contiguous");
+    TORCH_CHECK(x->stride(1) == x->size(2), who, ": head dim contiguous");
+    TORCH_CHECK(x->size(0) == q.size(0) && x->size(2) == q.size(2), who,
+                ": q/k/v row and head shapes");
+  }
+  TORCH_CHECK(!v || v->size(1) == k.size(1), who,
+              ": q/k/v row and head shapes");
+}
+
+// bf16 paged cache: kc/vc [n_pages, page, kh, hd] + int32 page table.
+static void check_kv_cache(const char* who, const torch::Tensor& kc,
+                           const torch::Tensor& vc,
+                           const torch::Tensor& page_table) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && page_table.is_cuda(), who,
+              ": cache and page table must be on GPU");
+  TORCH_CHECK(kc.scalar_type() == at::kBFloat16 &&
+                  vc.scalar_type() == at::kBFloat16,
+              who, ": cache must be bf16");
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() &&
+                  kc.sizes() == vc.sizes(),
+              who, ": caches contiguous [n_pages, page, kh, hd], same shape");
+  TORCH_CHECK(page_table.scalar_type() == at::kInt && page_table.dim() == 1 &&
+                  page_table.is_contiguous(),
+              who, ": page_table int32 [n_logical_pages]");
+}
+
+// fp8 (e4m3fn) paged cache: kc/vc uint8 [n_pages, page, kh, hd], ksc/vsc f32
+// [n_pages, kh, page] (kv_fp8.hip).
+static void check_fp8_cache(const char* who, const torch::Tensor& kc,
+                            const torch::Tensor& vc, const torch::Tensor& ksc,
+                            const torch::Tensor& vsc,
+                            const torch::Tensor& page_table) {
+  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && ksc.is_cuda() && vsc.is_cuda() &&
+                  page_table.is_cuda(),
+              who, ": cache, scales and page table must be on GPU");
+  TORCH_CHECK(kc.scalar_type() == at::kByte && vc.scalar_type() == at::kByte,
+              who, ": fp8 cache must be uint8 (e4m3fn bytes)");
+  TORCH_CHECK(ksc.scalar_type() == at::kFloat &&
+                  vsc.scalar_type() == at::kFloat,
+              who, ": cache scales must be f32");
+  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() &&
+                  kc.sizes() == vc.sizes(),
+              who, ": caches contiguous [n_pages, page, kh, hd], same shape");
+  TORCH_CHECK(ksc.dim() == 3 && ksc.is_contiguous() && vsc.is_contiguous() &&
+                  ksc.sizes() == vsc.sizes() && ksc.size(0) == kc.size(0) &&
+                  ksc.size(1) == kc.size(2) && ksc.size(2) == kc.size(1),
+              who, ": scales contiguous [n_pages, kh, page]");
+  const int64_t hd = kc.size(3);
+  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, who, ": hd in {32, 64, 128}");
+  TORCH_CHECK(page_table.scalar_type() == at::kInt && page_table.dim() == 1 &&
+                  page_table.is_contiguous(),
+              who, ": page_table int32 [n_logical_pages]");
+}
+
+// k (and v) rows must fit the cache they are appended to.
+static void check_cache_matches(const char* who, const torch::Tensor& kc,
+                                const torch::Tensor& k) {
+  TORCH_CHECK(kc.size(2) == k.size(1) && kc.size(3) == k.size(2), who,
+              ": cache [.., kh, hd] must match k");
+}
+
+// --------------------------------------------------------------------------
 
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps,
-                      c10::optional<torch::Tensor> out) {
+                      OptTensor out) {
   CHECK_BF16_CUDA(x);
   CHECK_BF16_CUDA(w);
   auto xc = x.contiguous();
@@ -158,19 +185,14 @@ torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor w, double eps,
   const int t = xc.numel() / d;
   TORCH_CHECK(d % 8 == 0, "rmsnorm: d must be a multiple of 8");
   auto y = out.has_value() ? *out : torch::empty_like(xc);
-  // decode-sized calls (1-4 rows): a single 256-thread block is
-  // latency-bound under a loaded memory system (rocprof: 12.6 us avg at
-  // 3-opponent concurrency) — 4x the threads quarters the serial depth
-  const int thr = t <= 4 ? 1024 : 256;
-  rmsnorm_kernel<<<t, thr, 0, cur_stream()>>>(uptr(xc), uptr(wc), uptr_mut(y),
-                                              d, (float)eps);
+  launch_rmsnorm(uptr(xc), uptr(wc), uptr_mut(y), t, d, (float)eps,
+                 cur_stream());
   return y;
 }
 
 std::tuple<torch::Tensor, torch::Tensor> add_rmsnorm(
     torch::Tensor resid, torch::Tensor delta, torch::Tensor w, double eps,
-    c10::optional<torch::Tensor> out_resid,
-    c10::optional<torch::Tensor> out_y) {
+    OptTensor out_resid, OptTensor out_y) {
   CHECK_BF16_CUDA(resid);
   CHECK_BF16_CUDA(delta);
   CHECK_BF16_CUDA(w);
@@ -182,84 +204,53 @@ std::tuple<torch::Tensor, torch::Tensor> add_rmsnorm(
   TORCH_CHECK(d % 8 == 0, "add_rmsnorm: d must be a multiple of 8");
   auto r_out = out_resid.has_value() ? *out_resid : torch::empty_like(rc);
   auto y = out_y.has_value() ? *out_y : torch::empty_like(rc);
-  const int thr = t <= 4 ? 1024 : 256;  // see rmsnorm
-  add_rmsnorm_kernel<<<t, thr, 0, cur_stream()>>>(
-      uptr(rc), uptr(dc), uptr(wc), uptr_mut(r_out), uptr_mut(y), d, (float)eps);
+  launch_add_rmsnorm(uptr(rc), uptr(dc), uptr(wc), uptr_mut(r_out),
+                     uptr_mut(y), t, d, (float)eps, cur_stream());
   return {r_out, y};
 }
 
+// RoPE in place on q/k (interleaved pairs, table-driven). pos_state (int32[1]
+// on device) replaces pos0 in graph mode.
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor cost,
-                  torch::Tensor sint, int64_t pos0) {
-  CHECK_BF16_CUDA(q);
-  CHECK_BF16_CUDA(k);
-  // q/k may be strided VIEWS of the fused QKV output: [t, h, hd] with an
-  // arbitrary row stride but contiguous head/dim dims.
-  TORCH_CHECK(q.stride(2) == 1 && k.stride(2) == 1, "rope: dim contiguous");
-  TORCH_CHECK(q.stride(1) == q.size(2) && k.stride(1) == k.size(2),
-              "rope: head dim contiguous");
-  TORCH_CHECK(cost.scalar_type() == at::kFloat, "rope: cos table f32");
+                  torch::Tensor sint, int64_t pos0,
+                  const OptTensor& pos_state) {
+  check_qkv_views("rope", q, k, nullptr);
   const int t = q.size(0), hq = q.size(1), hd = q.size(2);
   const int hk = k.size(1);
-  TORCH_CHECK(hd % 2 == 0);
-  const int waves = t * (hq + hk);
-  const int blocks = (waves * 64 + 255) / 256;
-  rope_kernel<<<blocks, 256, 0, cur_stream()>>>(
-      uptr_mut(q), uptr_mut(k), cost.data_ptr<float>(), sint.data_ptr<float>(),
-      t, hq, hk, hd, (int)pos0, q.stride(0), k.stride(0), nullptr);
-}
-
-// graph-mode RoPE: position read from a device int32 word
-void rope_inplace_ds(torch::Tensor q, torch::Tensor k, torch::Tensor cost,
-                     torch::Tensor sint, torch::Tensor pos_state) {
-  CHECK_BF16_CUDA(q);
-  const int t = q.size(0), hq = q.size(1), hd = q.size(2);
-  const int hk = k.size(1);
-  const int waves = t * (hq + hk);
-  const int blocks = (waves * 64 + 255) / 256;
-  rope_kernel<<<blocks, 256, 0, cur_stream()>>>(
-      uptr_mut(q), uptr_mut(k), cost.data_ptr<float>(), sint.data_ptr<float>(),
-      t, hq, hk, hd, 0, q.stride(0), k.stride(0), pos_state.data_ptr<int>());
+  TORCH_CHECK(hd % 2 == 0, "rope: hd even");
+  check_rope_tables("rope", cost, sint, hd);
+  const int* pp = check_pos_state("rope", pos_state);
+  if (!pp) check_host_pos("rope", pos0, t, &cost, nullptr, 0);
+  launch_rope(uptr_mut(q), uptr_mut(k), cost.data_ptr<float>(),
+              sint.data_ptr<float>(), t, hq, hk, hd, (int)pos0,
+              q.stride(0), k.stride(0), pp, cur_stream());
 }
 
 // Fused RoPE + paged KV scatter: rotate q/k in place AND write the rotated
 // k plus v into the page pool in one launch (saves a kernel + a K re-read
-// per layer on the kernel-count-bound decode path). pos_state (int32[1] on
-// device) replaces pos0 in graph mode.
+// per layer on the kernel-count-bound decode path).
 void rope_kv(torch::Tensor q, torch::Tensor k, torch::Tensor v,
              torch::Tensor cost, torch::Tensor sint, torch::Tensor kc,
              torch::Tensor vc, torch::Tensor page_table, int64_t pos0,
-             const c10::optional<torch::Tensor>& pos_state) {
-  CHECK_BF16_CUDA(q);
-  CHECK_BF16_CUDA(k);
-  CHECK_BF16_CUDA(kc);
-  TORCH_CHECK(q.stride(2) == 1 && k.stride(2) == 1 && v.stride(2) == 1,
-              "rope_kv: dim contiguous");
-  TORCH_CHECK(q.stride(1) == q.size(2) && k.stride(1) == k.size(2) &&
-                  v.stride(1) == v.size(2),
-              "rope_kv: head dim contiguous");
-  TORCH_CHECK(cost.scalar_type() == at::kFloat, "rope_kv: cos table f32");
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), "cache contiguous");
-  TORCH_CHECK(page_table.scalar_type() == at::kInt);
+             const OptTensor& pos_state) {
+  check_qkv_views("rope_kv", q, k, &v);
+  check_kv_cache("rope_kv", kc, vc, page_table);
+  check_cache_matches("rope_kv", kc, k);
   const int t = q.size(0), hq = q.size(1), hd = q.size(2);
   const int hk = k.size(1);
   const int page = kc.size(1);
   TORCH_CHECK(hd % 16 == 0, "rope_kv: hd % 16 == 0");
-  const int waves = t * (hq + 2 * hk);
-  const int* pp = pos_state.has_value() ? pos_state->data_ptr<int>() : nullptr;
-  // decode (t==1): one wave per 64-thread block spreads the ~48
-  // latency-bound slot-waves over 4x the CUs (the 12-block launch
-  // measured 11.6 us avg under 3-opponent concurrency)
-  const int thr = t <= 2 ? 64 : 256;
-  const int blocks = (waves * 64 + thr - 1) / thr;
-  rope_kv_kernel<<<blocks, thr, 0, cur_stream()>>>(
-      uptr_mut(q), uptr_mut(k), uptr(v), cost.data_ptr<float>(),
-      sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
-      page_table.data_ptr<int>(), t, hq, hk, hd, (int)pos0, q.stride(0),
-      k.stride(0), v.stride(0), page, pp);
+  check_rope_tables("rope_kv", cost, sint, hd);
+  const int* pp = check_pos_state("rope_kv", pos_state);
+  if (!pp) check_host_pos("rope_kv", pos0, t, &cost, &page_table, page);
+  launch_rope_kv(uptr_mut(q), uptr_mut(k), uptr(v), cost.data_ptr<float>(),
+                 sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
+                 page_table.data_ptr<int>(), t, hq, hk, hd, (int)pos0,
+                 q.stride(0), k.stride(0), v.stride(0), page, pp,
+                 cur_stream());
 }
 
-torch::Tensor swiglu(torch::Tensor gate, torch::Tensor up,
-                     c10::optional<torch::Tensor> out_opt) {
+torch::Tensor swiglu(torch::Tensor gate, torch::Tensor up, OptTensor out_opt) {
   CHECK_BF16_CUDA(gate);
   CHECK_BF16_CUDA(up);
   TORCH_CHECK(gate.dim() == 2 && up.dim() == 2);
@@ -270,40 +261,32 @@ torch::Tensor swiglu(torch::Tensor gate, torch::Tensor up,
   const int t = gate.size(0), f = gate.size(1);
   TORCH_CHECK(f % 8 == 0);
   auto out = out_opt.has_value() ? *out_opt : torch::empty({t, f}, gate.options());
-  const long nvec = (long)t * f / 8;
-  const int blocks = (int)std::min<long>((nvec + 255) / 256, 8192);
-  swiglu_kernel<<<blocks, 256, 0, cur_stream()>>>(
-      uptr(gate), uptr(up), uptr_mut(out), t, f, (int)gate.stride(0));
+  launch_swiglu(uptr(gate), uptr(up), uptr_mut(out), t, f,
+                (int)gate.stride(0), cur_stream());
   return out;
 }
 
+// Paged KV scatter of t fresh rows k, v [t, kh, hd] at pos0 (pos_state in
+// graph mode).
 void kv_write(torch::Tensor kc, torch::Tensor vc, torch::Tensor page_table,
-              int64_t pos0, torch::Tensor k, torch::Tensor v) {
-  CHECK_BF16_CUDA(kc);
+              int64_t pos0, torch::Tensor k, torch::Tensor v,
+              const OptTensor& pos_state) {
+  check_kv_cache("kv_write", kc, vc, page_table);
   CHECK_BF16_CUDA(k);
-  TORCH_CHECK(page_table.scalar_type() == at::kInt);
-  auto kcc = kc;  // [np, page, kh, hd] must already be contiguous
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), "cache contiguous");
+  CHECK_BF16_CUDA(v);
+  TORCH_CHECK(k.dim() == 3 && k.sizes() == v.sizes(),
+              "kv_write: k, v [t, kh, hd], same shape");
+  check_cache_matches("kv_write", kc, k);
   auto kq = k.contiguous();
   auto vq = v.contiguous();
   const int t = kq.size(0), kh = kq.size(1), hd = kq.size(2);
   const int page = kc.size(1);
-  TORCH_CHECK((kh * hd) % 8 == 0);
-  kv_write_kernel<<<t, 256, 0, cur_stream()>>>(
-      uptr(kq), uptr(vq), uptr_mut(kcc), uptr_mut(vc),
-      page_table.data_ptr<int>(), (int)pos0, t, kh, hd, page, nullptr);
-}
-
-void kv_write_ds(torch::Tensor kc, torch::Tensor vc, torch::Tensor page_table,
-                 torch::Tensor pos_state, torch::Tensor k, torch::Tensor v) {
-  auto kq = k.contiguous();
-  auto vq = v.contiguous();
-  const int t = kq.size(0), kh = kq.size(1), hd = kq.size(2);
-  const int page = kc.size(1);
-  kv_write_kernel<<<t, 256, 0, cur_stream()>>>(
-      uptr(kq), uptr(vq), uptr_mut(kc), uptr_mut(vc),
-      page_table.data_ptr<int>(), 0, t, kh, hd, page,
-      pos_state.data_ptr<int>());
+  TORCH_CHECK((kh * hd) % 8 == 0, "kv_write: kh*hd % 8 == 0");
+  const int* pp = check_pos_state("kv_write", pos_state);
+  if (!pp) check_host_pos("kv_write", pos0, t, nullptr, &page_table, page);
+  launch_kv_write(uptr(kq), uptr(vq), uptr_mut(kc), uptr_mut(vc),
+                  page_table.data_ptr<int>(), (int)pos0, t, kh, hd,
+                  page, pp, cur_stream());
 }
 
 torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -381,8 +364,7 @@ torch::Tensor mfma_probe16(torch::Tensor a, torch::Tensor b) {
   auto d = torch::empty({16, 16}, torch::TensorOptions()
                                       .dtype(at::kFloat)
                                       .device(a.device()));
-  mfma_probe_16x16x32<<<1, 64, 0, cur_stream()>>>(uptr(ac), uptr(bc),
-                                                  d.data_ptr<float>());
+  launch_mfma_probe16(uptr(ac), uptr(bc), d.data_ptr<float>(), cur_stream());
   return d;
 }
 
@@ -422,38 +404,90 @@ py::tuple decode_split_geometry(int64_t seq, int64_t kh,
   return py::make_tuple(n_splits, split_len);
 }
 
+// Everything of a decode-attention call that is not the kernel launch, shared
+// by the bf16 and fp8 entries (the caller has already run its cache checker):
+// q and out handling, the split geometry, the per-cache workspace and the
+// bound-versus-coverage check. `bound` is seq_len: the host length, or with
+// pos_state the static bound (max_seq) that sizes the splits so the launch
+// geometry is replay-stable; the true length is then *pos_state + 1
+// in-kernel.
+struct DecodeCall {
+  torch::Tensor qc, out;
+  DecodeSplitArgs a;
+};
+static DecodeCall decode_prepare(const char* who, const torch::Tensor& q,
+                                 const torch::Tensor& kc,
+                                 const torch::Tensor& page_table,
+                                 int64_t bound, double scale,
+                                 const OptTensor& pos_state,
+                                 const OptTensor& out_opt, bool identity,
+                                 int64_t split_blocks) {
+  CHECK_BF16_CUDA(q);
+  TORCH_CHECK(q.dim() == 2, who, ": q [hq, hd]");
+  DecodeCall c;
+  c.qc = q.contiguous();
+  const int hq = c.qc.size(0), hd = c.qc.size(1);
+  const int page = kc.size(1), kh = kc.size(2);
+  TORCH_CHECK(kc.size(3) == hd, who, ": q and cache head dims differ");
+  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, who, ": hd in {32, 64, 128}");
+  TORCH_CHECK(hq % kh == 0 && hq / kh <= 8, who, ": GQA group <= 8");
+  const int group = hq / kh;
+  const int64_t covered =
+      (identity ? kc.size(0) : page_table.numel()) * (int64_t)page;
+  TORCH_CHECK(bound >= 1 && bound <= covered, who,
+              ": seq_len outside the cache");
+  const int* pos_ptr = check_pos_state(who, pos_state);
+  if (out_opt.has_value()) {
+    c.out = *out_opt;
+    TORCH_CHECK(c.out.is_cuda() && c.out.scalar_type() == at::kBFloat16 &&
+                    c.out.is_contiguous() &&
+                    c.out.numel() == (int64_t)hq * hd,
+                who, ": out must be contiguous bf16 [hq, hd]");
+  } else {
+    c.out = torch::empty({hq, hd}, c.qc.options());
+  }
+  int n_splits, split_len;
+  split_geometry(bound, kh, (int)split_blocks, &n_splits, &split_len);
+  const long khnsg = (long)kh * n_splits * group;
+  float* ws = decode_workspace(kc, khnsg, hd, q.device());
+  c.a = {page_table.data_ptr<int>(), pos_ptr, (int)bound, (float)scale, kh,
+         group, hd, page, split_len, n_splits, ws, ws + khnsg,
+         ws + 2 * khnsg, identity ? 1 : 0};
+  return c;
+}
+
 torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kc,
                                 torch::Tensor vc, torch::Tensor page_table,
                                 int64_t seq_len, double scale,
-                                bool identity, int64_t split_blocks) {
-  CHECK_BF16_CUDA(q);
-  CHECK_BF16_CUDA(kc);
-  auto qc = q.contiguous();
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous());
-  TORCH_CHECK(page_table.scalar_type() == at::kInt);
-  const int hq = qc.size(0), hd = qc.size(1);
-  const int page = kc.size(1), kh = kc.size(2);
-  const int group = hq / kh;
-  TORCH_CHECK(group <= 8, "GQA group <= 8");
-  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128);
+                                const OptTensor& pos_state,
+                                const OptTensor& out, bool identity,
+                                int64_t split_blocks) {
+  check_kv_cache("attn_decode_paged", kc, vc, page_table);
+  DecodeCall c =
+      decode_prepare("attn_decode_paged", q, kc, page_table, seq_len, scale,
+                     pos_state, out, identity, split_blocks);
+  launch_attn_decode_split(uptr(c.qc), uptr(kc), uptr(vc), c.a,
+                           uptr_mut(c.out), cur_stream());
+  return c.out;
+}
 
-  int n_splits, split_len;
-  split_geometry(seq_len, kh, (int)split_blocks, &n_splits, &split_len);
-  auto out = torch::empty({hq, hd}, qc.options());
-  const long khnsg = (long)kh * n_splits * group;
-  auto stream = cur_stream();
-  float* ws;
-  {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    auto& w = g_ws[(void*)kc.data_ptr()];
-    ws = ws_f32(w.attn_ws, w.retired, khnsg * (2 + hd), q.device());
-  }
-  launch_attn_decode_split(uptr(qc), uptr(kc), uptr(vc),
-                           page_table.data_ptr<int>(), (int)seq_len,
-                           (float)scale, kh, group, hd, page, split_len,
-                           n_splits, ws, ws + khnsg, ws + 2 * khnsg,
-                           nullptr, uptr_mut(out), identity ? 1 : 0, stream);
-  return out;
+// Same over an fp8 cache; the dequantization is folded into the split kernel.
+torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kc,
+                                    torch::Tensor vc, torch::Tensor ksc,
+                                    torch::Tensor vsc,
+                                    torch::Tensor page_table, int64_t seq_len,
+                                    double scale, const OptTensor& pos_state,
+                                    const OptTensor& out, bool identity,
+                                    int64_t split_blocks) {
+  check_fp8_cache("attn_decode_paged_fp8", kc, vc, ksc, vsc, page_table);
+  DecodeCall c =
+      decode_prepare("attn_decode_paged_fp8", q, kc, page_table, seq_len,
+                     scale, pos_state, out, identity, split_blocks);
+  launch_attn_decode_split_fp8(uptr(c.qc), kc.data_ptr<uint8_t>(),
+                               vc.data_ptr<uint8_t>(), ksc.data_ptr<float>(),
+                               vsc.data_ptr<float>(), c.a, uptr_mut(c.out),
+                               cur_stream());
+  return c.out;
 }
 
 // Async variant: write the sampled token id into out[idx] (int32, on
@@ -464,15 +498,14 @@ void sample_to(torch::Tensor logits, double temp, int64_t seed,
   CHECK_BF16_CUDA(logits);
   TORCH_CHECK(out.scalar_type() == at::kInt && out.is_cuda());
   auto lc = logits.contiguous();
-  sample_kernel<<<1, 1024, 0, cur_stream()>>>(
-      uptr(lc), (int)lc.numel(), (float)temp, (uint32_t)seed,
-      out.data_ptr<int>() + idx);
+  launch_sample(uptr(lc), (int)lc.numel(), (float)temp, (uint32_t)seed,
+                out.data_ptr<int>() + idx, cur_stream());
 }
 
 // Decode GEMV: y = x @ w for batch-1 x. Streams w once at HBM rate
 // (hipBLASLt batch-1 measured 0.9-1.7 TB/s; this path targets ~5 TB/s).
 torch::Tensor gemv(torch::Tensor x, torch::Tensor w,
-                   c10::optional<torch::Tensor> out_opt) {
+                   OptTensor out_opt) {
   // y = x @ w^T with w stored row-major [N, K] (HF layout)
   CHECK_BF16_CUDA(x);
   CHECK_BF16_CUDA(w);
@@ -509,7 +542,7 @@ void gemv_gateup(torch::Tensor x, torch::Tensor w, torch::Tensor act) {
 // Replaces the separate (add_)rmsnorm launch before every consuming decode
 // GEMV (see gemv.hip fusion comment).
 torch::Tensor gemv_norm(torch::Tensor x, torch::Tensor wln, torch::Tensor w,
-                        double eps, c10::optional<torch::Tensor> out_opt) {
+                        double eps, OptTensor out_opt) {
   CHECK_BF16_CUDA(x);
   CHECK_BF16_CUDA(wln);
   CHECK_BF16_CUDA(w);
@@ -533,55 +566,33 @@ torch::Tensor gemv_norm(torch::Tensor x, torch::Tensor wln, torch::Tensor w,
 }
 
 // Preconditions shared by the two qkv GEMVs whose epilogue rotates and
-// appends to the KV cache (rope_epilogue.h). Returns (hd, page, pos_ptr);
+// appends to the KV cache (rope_epilogue.h). Returns the epilogue operands;
 // a shape outside them belongs on the gemv + rope_kv pair.
-struct RopeKvGeom { int hd, page; const int* pos_ptr; };
-static RopeKvGeom check_rope_kv_epilogue(
+static RopeKvArgs check_rope_kv_epilogue(
     const char* op, int N, int64_t hq, int64_t kh, const torch::Tensor& cost,
-    const torch::Tensor& sint, const torch::Tensor& kc,
-    const torch::Tensor& vc, const torch::Tensor& page_table, int64_t pos0,
-    const c10::optional<torch::Tensor>& pos_state, const torch::Tensor& y) {
+    const torch::Tensor& sint, torch::Tensor& kc, torch::Tensor& vc,
+    const torch::Tensor& page_table, int64_t pos0, const OptTensor& pos_state,
+    const torch::Tensor& y) {
   TORCH_CHECK(hq >= 1 && kh >= 1 && N % (hq + 2 * kh) == 0, op,
               ": N == (hq + 2*kh)*hd");
   const int hd = N / (int)(hq + 2 * kh);
   TORCH_CHECK(hd % 16 == 0, op, ": hd % 16 == 0");
   TORCH_CHECK(N <= 8192, op, ": w32 geometry only (N <= 8192)");
-  TORCH_CHECK(cost.is_cuda() && sint.is_cuda() &&
-                  cost.scalar_type() == at::kFloat &&
-                  sint.scalar_type() == at::kFloat,
-              op, ": cos/sin tables f32 on GPU");
-  TORCH_CHECK(cost.dim() == 2 && cost.is_contiguous() &&
-                  sint.is_contiguous() && cost.sizes() == sint.sizes() &&
-                  cost.size(1) == hd / 2,
-              op, ": cos/sin tables [max_pos, hd/2] contiguous");
-  CHECK_BF16_CUDA(kc);
-  CHECK_BF16_CUDA(vc);
-  TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous(), op,
-              ": caches contiguous");
-  TORCH_CHECK(kc.dim() == 4 && kc.sizes() == vc.sizes() && kc.size(2) == kh &&
-                  kc.size(3) == hd,
-              op, ": caches [n_pages, page, kh, hd]");
-  TORCH_CHECK(page_table.is_cuda() && page_table.scalar_type() == at::kInt &&
-                  page_table.is_contiguous(),
-              op, ": page_table int32 on GPU");
+  check_rope_tables(op, cost, sint, hd);
+  check_kv_cache(op, kc, vc, page_table);
+  TORCH_CHECK(kc.size(2) == kh && kc.size(3) == hd, op,
+              ": caches [n_pages, page, kh, hd]");
   const int page = kc.size(1);
-  const int* pp = nullptr;
-  if (pos_state.has_value()) {
-    TORCH_CHECK(pos_state->is_cuda() && pos_state->scalar_type() == at::kInt &&
-                    pos_state->numel() >= 1,
-                op, ": pos_state int32 word on GPU");
-    pp = pos_state->data_ptr<int>();
-  } else {
-    TORCH_CHECK(pos0 >= 0 && pos0 < cost.size(0) &&
-                    pos0 / page < page_table.numel(),
-                op, ": pos inside the rope table and the page table");
-  }
+  const int* pp = check_pos_state(op, pos_state);
+  if (!pp) check_host_pos(op, pos0, 1, &cost, &page_table, page);
   CHECK_BF16_CUDA(y);
   TORCH_CHECK(y.is_contiguous() && (long)y.numel() == (long)N, op,
               ": out contiguous, numel == N");
   TORCH_CHECK(reinterpret_cast<uintptr_t>(y.data_ptr()) % 4 == 0, op,
               ": out 4-byte aligned (pairs are stored as one word)");
-  return {hd, page, pp};
+  return {cost.data_ptr<float>(), sint.data_ptr<float>(), uptr_mut(kc),
+          uptr_mut(vc), page_table.data_ptr<int>(), pp, (int)pos0, (int)hq,
+          (int)kh, hd, page};
 }
 
 // qkv projection + RoPE + KV append in one launch (bf16 weights):
@@ -592,8 +603,8 @@ torch::Tensor gemv_norm_rope_kv(
     torch::Tensor x, torch::Tensor wln, torch::Tensor w, double eps,
     torch::Tensor cost, torch::Tensor sint, torch::Tensor kc, torch::Tensor vc,
     torch::Tensor page_table, int64_t pos0, int64_t hq, int64_t kh,
-    const c10::optional<torch::Tensor>& pos_state,
-    c10::optional<torch::Tensor> out_opt) {
+    const OptTensor& pos_state,
+    OptTensor out_opt) {
   CHECK_BF16_CUDA(x);
   CHECK_BF16_CUDA(wln);
   CHECK_BF16_CUDA(w);
@@ -607,14 +618,11 @@ torch::Tensor gemv_norm_rope_kv(
   auto xc = x.contiguous();
   auto lc = wln.contiguous();
   auto y = out_opt.has_value() ? *out_opt : torch::empty({1, N}, x.options());
-  const RopeKvGeom g = check_rope_kv_epilogue(
+  const RopeKvArgs ra = check_rope_kv_epilogue(
       "gemv_norm_rope_kv", N, hq, kh, cost, sint, kc, vc, page_table, pos0,
       pos_state, y);
   launch_gemv_norm_rope_kv(uptr(xc), uptr(lc), uptr(w), uptr_mut(y), K,
-                           (float)eps, cost.data_ptr<float>(),
-                           sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
-                           page_table.data_ptr<int>(), g.pos_ptr, (int)pos0,
-                           (int)hq, (int)kh, g.hd, g.page, cur_stream());
+                           (float)eps, ra, cur_stream());
   return y;
 }
 
@@ -626,7 +634,7 @@ void gemv_fp8_q_rope_kv(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
                         torch::Tensor kc, torch::Tensor vc,
                         torch::Tensor page_table, int64_t pos0, int64_t hq,
                         int64_t kh,
-                        const c10::optional<torch::Tensor>& pos_state) {
+                        const OptTensor& pos_state) {
   TORCH_CHECK(w8.dim() == 2 && w8.is_contiguous() && w8.is_cuda() &&
               w8.scalar_type() == at::kByte);
   const int N = w8.size(0), K = w8.size(1);
@@ -637,15 +645,12 @@ void gemv_fp8_q_rope_kv(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
               xs.scalar_type() == at::kFloat);
   TORCH_CHECK(wsc.is_cuda() && wsc.numel() >= N &&
               wsc.scalar_type() == at::kFloat && wsc.is_contiguous());
-  const RopeKvGeom g = check_rope_kv_epilogue(
+  const RopeKvArgs ra = check_rope_kv_epilogue(
       "gemv_fp8_q_rope_kv", N, hq, kh, cost, sint, kc, vc, page_table, pos0,
       pos_state, out);
   launch_gemv_fp8_rope_kv(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                           w8.data_ptr<uint8_t>(), wsc.data_ptr<float>(),
-                          uptr_mut(out), K, cost.data_ptr<float>(),
-                          sint.data_ptr<float>(), uptr_mut(kc), uptr_mut(vc),
-                          page_table.data_ptr<int>(), g.pos_ptr, (int)pos0,
-                          (int)hq, (int)kh, g.hd, g.page, cur_stream());
+                          uptr_mut(out), K, ra, cur_stream());
 }
 
 // residual-add fused into the GEMV epilogue: resid += x @ w^T (in place).
@@ -909,44 +914,9 @@ int64_t sample(torch::Tensor logits, double temp, double top_p, int64_t seed) {
   auto out = torch::empty({1}, torch::TensorOptions()
                                    .dtype(at::kInt)
                                    .device(logits.device()));
-  sample_kernel<<<1, 1024, 0, cur_stream()>>>(uptr(lc), vocab, (float)temp,
-                                             (uint32_t)seed,
-                                             out.data_ptr<int>());
+  launch_sample(uptr(lc), vocab, (float)temp, (uint32_t)seed,
+                out.data_ptr<int>(), cur_stream());
   return out.cpu().item<int>();
-}
-
-// graph-mode decode attention: seq_len = *pos_state + 1 in-kernel; split
-// count is sized once for the WHOLE generation (max_seq bound) so the
-// launch geometry is replay-stable.
-torch::Tensor attn_decode_paged_ds(torch::Tensor q, torch::Tensor kc,
-                                   torch::Tensor vc, torch::Tensor page_table,
-                                   torch::Tensor pos_state, int64_t max_seq,
-                                   double scale,
-                                   c10::optional<torch::Tensor> out_opt,
-                                   bool identity, int64_t split_blocks) {
-  CHECK_BF16_CUDA(q);
-  auto qc = q.contiguous();
-  const int hq = qc.size(0), hd = qc.size(1);
-  const int page = kc.size(1), kh = kc.size(2);
-  const int group = hq / kh;
-  int n_splits, split_len;
-  split_geometry(max_seq, kh, (int)split_blocks, &n_splits, &split_len);
-  auto out = out_opt.has_value() ? *out_opt : torch::empty({hq, hd}, qc.options());
-  const long khnsg = (long)kh * n_splits * group;
-  auto stream = cur_stream();
-  float* ws;
-  {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    auto& w = g_ws[(void*)kc.data_ptr()];
-    ws = ws_f32(w.attn_ws, w.retired, khnsg * (2 + hd), q.device());
-  }
-  launch_attn_decode_split(uptr(qc), uptr(kc), uptr(vc),
-                           page_table.data_ptr<int>(), (int)max_seq,
-                           (float)scale, kh, group, hd, page, split_len,
-                           n_splits, ws, ws + khnsg, ws + 2 * khnsg,
-                           pos_state.data_ptr<int>(), uptr_mut(out),
-                           identity ? 1 : 0, stream);
-  return out;
 }
 
 void sample_state(torch::Tensor logits, torch::Tensor temp_state,
@@ -958,11 +928,12 @@ void sample_state(torch::Tensor logits, torch::Tensor temp_state,
   TORCH_CHECK(tok_long.scalar_type() == at::kLong,
               "sample_state: tok_long must be int64 (the embedding index)");
   auto lc = logits.contiguous();
-  sample_state_kernel<<<1, 1024, 0, cur_stream()>>>(
+  launch_sample_state(
       uptr(lc), (int)lc.numel(), temp_state.data_ptr<float>(),
       reinterpret_cast<uint32_t*>(rng_state.data_ptr<int>()),
       tok_hist.data_ptr<int>(), step_state.data_ptr<int>(),
-      reinterpret_cast<long long*>(tok_long.data_ptr<int64_t>()));
+      reinterpret_cast<long long*>(tok_long.data_ptr<int64_t>()),
+      cur_stream());
 }
 
 // Release the decode-attention scratch entries whose keys (per-layer KV
@@ -986,81 +957,22 @@ void ws_release(torch::Tensor kc_all) {
   }
 }
 
-// --------------------------------------------------------------------------
-// fp8 (e4m3fn) KV cache: kc/vc uint8 [n_pages, page, kh, hd], ksc/vsc f32
-// [n_pages, kh, page] (kv_fp8.hip). The decode entries share split_geometry,
-// the combine kernel and the per-cache workspace map (keyed by the K-cache
-// pointer) with the bf16 ones.
-
-static void check_fp8_cache(const char* who, const torch::Tensor& kc,
-                            const torch::Tensor& vc, const torch::Tensor& ksc,
-                            const torch::Tensor& vsc,
-                            const torch::Tensor& page_table) {
-  TORCH_CHECK(kc.is_cuda() && vc.is_cuda() && ksc.is_cuda() && vsc.is_cuda() &&
-                  page_table.is_cuda(),
-              who, ": cache, scales and page table must be on GPU");
-  TORCH_CHECK(kc.scalar_type() == at::kByte && vc.scalar_type() == at::kByte,
-              who, ": fp8 cache must be uint8 (e4m3fn bytes)");
-  TORCH_CHECK(ksc.scalar_type() == at::kFloat &&
-                  vsc.scalar_type() == at::kFloat,
-              who, ": cache scales must be f32");
-  TORCH_CHECK(kc.dim() == 4 && kc.is_contiguous() && vc.is_contiguous() &&
-                  kc.sizes() == vc.sizes(),
-              who, ": caches contiguous [n_pages, page, kh, hd], same shape");
-  TORCH_CHECK(ksc.dim() == 3 && ksc.is_contiguous() && vsc.is_contiguous() &&
-                  ksc.sizes() == vsc.sizes() && ksc.size(0) == kc.size(0) &&
-                  ksc.size(1) == kc.size(2) && ksc.size(2) == kc.size(1),
-              who, ": scales contiguous [n_pages, kh, page]");
-  const int64_t hd = kc.size(3);
-  TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, who, ": hd in {32, 64, 128}");
-  TORCH_CHECK(page_table.scalar_type() == at::kInt && page_table.dim() == 1 &&
-                  page_table.is_contiguous(),
-              who, ": page_table int32 [n_logical_pages]");
-}
-
 // fp8 twin of rope_kv: rotate q/k in place (bit-identical to rope_kv) and
 // append the rowwise-quantized rotated k and v plus their scales.
 void rope_kv_fp8(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                  torch::Tensor cost, torch::Tensor sint, torch::Tensor kc,
                  torch::Tensor vc, torch::Tensor ksc, torch::Tensor vsc,
                  torch::Tensor page_table, int64_t pos0,
-                 const c10::optional<torch::Tensor>& pos_state) {
-  CHECK_BF16_CUDA(q);
-  CHECK_BF16_CUDA(k);
-  CHECK_BF16_CUDA(v);
+                 const OptTensor& pos_state) {
+  check_qkv_views("rope_kv_fp8", q, k, &v);
   check_fp8_cache("rope_kv_fp8", kc, vc, ksc, vsc, page_table);
-  TORCH_CHECK(q.dim() == 3 && k.dim() == 3 && v.dim() == 3,
-              "rope_kv_fp8: q/k/v [t, heads, hd]");
-  TORCH_CHECK(q.stride(2) == 1 && k.stride(2) == 1 && v.stride(2) == 1,
-              "rope_kv_fp8: dim contiguous");
-  TORCH_CHECK(q.stride(1) == q.size(2) && k.stride(1) == k.size(2) &&
-                  v.stride(1) == v.size(2),
-              "rope_kv_fp8: head dim contiguous");
+  check_cache_matches("rope_kv_fp8", kc, k);
   const int t = q.size(0), hq = q.size(1), hd = q.size(2);
   const int hk = k.size(1);
   const int page = kc.size(1);
-  TORCH_CHECK(k.size(0) == t && v.size(0) == t && v.size(1) == hk &&
-                  k.size(2) == hd && v.size(2) == hd,
-              "rope_kv_fp8: q/k/v row and head shapes");
-  TORCH_CHECK(kc.size(2) == hk && kc.size(3) == hd,
-              "rope_kv_fp8: cache [.., kh, hd] must match k");
-  TORCH_CHECK(cost.is_cuda() && sint.is_cuda() &&
-                  cost.scalar_type() == at::kFloat &&
-                  sint.scalar_type() == at::kFloat && cost.dim() == 2 &&
-                  cost.is_contiguous() && sint.is_contiguous() &&
-                  cost.sizes() == sint.sizes() && cost.size(1) == hd / 2,
-              "rope_kv_fp8: cos/sin tables f32 contiguous [max_pos, hd/2]");
-  const int* pp = nullptr;
-  if (pos_state.has_value()) {
-    TORCH_CHECK(pos_state->is_cuda() && pos_state->scalar_type() == at::kInt &&
-                    pos_state->numel() >= 1,
-                "rope_kv_fp8: pos_state must be a device int32 word");
-    pp = pos_state->data_ptr<int>();
-  } else {
-    TORCH_CHECK(pos0 >= 0 && pos0 + t <= cost.size(0) &&
-                    pos0 + t <= page_table.numel() * (int64_t)page,
-                "rope_kv_fp8: positions outside the tables");
-  }
+  check_rope_tables("rope_kv_fp8", cost, sint, hd);
+  const int* pp = check_pos_state("rope_kv_fp8", pos_state);
+  if (!pp) check_host_pos("rope_kv_fp8", pos0, t, &cost, &page_table, page);
   if (t == 0) return;
   launch_rope_kv_fp8(uptr_mut(q), uptr_mut(k), uptr(v), cost.data_ptr<float>(),
                      sint.data_ptr<float>(), kc.data_ptr<uint8_t>(),
@@ -1089,83 +1001,9 @@ std::tuple<torch::Tensor, torch::Tensor> kv_dequant_fp8(
   return {kout, vout};
 }
 
-// Shared body of the two fp8 decode entries. `bound` sizes the split
-// geometry (host length, or max_seq in graph mode where the true length is
-// *pos_state + 1 in-kernel).
-static torch::Tensor attn_decode_fp8_impl(
-    const char* who, torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
-    torch::Tensor ksc, torch::Tensor vsc, torch::Tensor page_table,
-    int64_t bound, double scale, const int* pos_ptr,
-    c10::optional<torch::Tensor> out_opt, bool identity,
-    int64_t split_blocks) {
-  CHECK_BF16_CUDA(q);
-  check_fp8_cache(who, kc, vc, ksc, vsc, page_table);
-  TORCH_CHECK(q.dim() == 2, who, ": q [hq, hd]");
-  auto qc = q.contiguous();
-  const int hq = qc.size(0), hd = qc.size(1);
-  const int page = kc.size(1), kh = kc.size(2);
-  TORCH_CHECK(kc.size(3) == hd, who, ": q and cache head dims differ");
-  TORCH_CHECK(hq % kh == 0 && hq / kh <= 8, who, ": GQA group <= 8");
-  const int group = hq / kh;
-  const int64_t covered =
-      (identity ? kc.size(0) : page_table.numel()) * (int64_t)page;
-  TORCH_CHECK(bound >= 1 && bound <= covered, who,
-              ": seq_len outside the cache");
-  int n_splits, split_len;
-  split_geometry(bound, kh, (int)split_blocks, &n_splits, &split_len);
-  torch::Tensor out;
-  if (out_opt.has_value()) {
-    out = *out_opt;
-    TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kBFloat16 &&
-                    out.is_contiguous() && out.numel() == (int64_t)hq * hd,
-                who, ": out must be contiguous bf16 [hq, hd]");
-  } else {
-    out = torch::empty({hq, hd}, qc.options());
-  }
-  const long khnsg = (long)kh * n_splits * group;
-  float* ws;
-  {
-    std::lock_guard<std::mutex> lk(g_ws_mu);
-    auto& w = g_ws[(void*)kc.data_ptr()];
-    ws = ws_f32(w.attn_ws, w.retired, khnsg * (2 + hd), q.device());
-  }
-  launch_attn_decode_split_fp8(
-      uptr(qc), kc.data_ptr<uint8_t>(), vc.data_ptr<uint8_t>(),
-      ksc.data_ptr<float>(), vsc.data_ptr<float>(), page_table.data_ptr<int>(),
-      (int)bound, (float)scale, kh, group, hd, page, split_len, n_splits, ws,
-      ws + khnsg, ws + 2 * khnsg, pos_ptr, uptr_mut(out), identity ? 1 : 0,
-      cur_stream());
-  return out;
-}
-
-torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kc,
-                                    torch::Tensor vc, torch::Tensor ksc,
-                                    torch::Tensor vsc,
-                                    torch::Tensor page_table, int64_t seq_len,
-                                    double scale, bool identity,
-                                    int64_t split_blocks) {
-  return attn_decode_fp8_impl("attn_decode_paged_fp8", q, kc, vc, ksc, vsc,
-                              page_table, seq_len, scale, nullptr,
-                              c10::nullopt, identity, split_blocks);
-}
-
-torch::Tensor attn_decode_paged_fp8_ds(
-    torch::Tensor q, torch::Tensor kc, torch::Tensor vc, torch::Tensor ksc,
-    torch::Tensor vsc, torch::Tensor page_table, torch::Tensor pos_state,
-    int64_t max_seq, double scale, c10::optional<torch::Tensor> out_opt,
-    bool identity, int64_t split_blocks) {
-  TORCH_CHECK(pos_state.is_cuda() && pos_state.scalar_type() == at::kInt &&
-                  pos_state.numel() >= 1,
-              "attn_decode_paged_fp8_ds: pos_state must be a device int32 word");
-  return attn_decode_fp8_impl("attn_decode_paged_fp8_ds", q, kc, vc, ksc, vsc,
-                              page_table, max_seq, scale,
-                              pos_state.data_ptr<int>(), out_opt, identity,
-                              split_blocks);
-}
-
 void bump(torch::Tensor pos_state, torch::Tensor step_state) {
-  bump_kernel<<<1, 64, 0, cur_stream()>>>(pos_state.data_ptr<int>(),
-                                          step_state.data_ptr<int>());
+  launch_bump(pos_state.data_ptr<int>(), step_state.data_ptr<int>(),
+              cur_stream());
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1175,10 +1013,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("add_rmsnorm", &add_rmsnorm, "fused residual add + RMSNorm",
         py::arg("resid"), py::arg("delta"), py::arg("w"), py::arg("eps"),
         py::arg("out_resid") = py::none(), py::arg("out_y") = py::none());
-  m.def("rope_inplace", &rope_inplace, "RoPE (interleaved pairs, table-driven)");
+  m.def("rope_inplace", &rope_inplace, "RoPE (interleaved pairs, table-driven)",
+        py::arg("q"), py::arg("k"), py::arg("cost"), py::arg("sint"),
+        py::arg("pos0"), py::arg("pos_state") = py::none());
   m.def("swiglu", &swiglu, "fused silu(gate)*up",
         py::arg("gate"), py::arg("up"), py::arg("out") = py::none());
-  m.def("kv_write", &kv_write, "paged KV scatter");
+  m.def("kv_write", &kv_write, "paged KV scatter",
+        py::arg("kc"), py::arg("vc"), py::arg("page_table"), py::arg("pos0"),
+        py::arg("k"), py::arg("v"), py::arg("pos_state") = py::none());
   m.def("attn_prefill", &attn_prefill, "causal prefill attention");
   m.def("attn_prefill_simple", &attn_prefill_simple, "non-MFMA prefill (anchor)");
   m.def("attn_prefill_ablate", &attn_prefill_ablate,
@@ -1186,8 +1028,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mfma_probe16", &mfma_probe16, "MFMA 16x16x32 fragment-map probe");
   m.def("attn_decode_paged", &attn_decode_paged, "paged decode attention",
         py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
-        py::arg("seq_len"), py::arg("scale"), py::arg("identity") = false,
-        py::arg("split_blocks") = 0);
+        py::arg("seq_len"), py::arg("scale"),
+        py::arg("pos_state") = py::none(), py::arg("out") = py::none(),
+        py::arg("identity") = false, py::arg("split_blocks") = 0);
   m.def("decode_split_geometry", &decode_split_geometry,
         "decode split geometry query -> (n_splits, split_len)",
         py::arg("seq"), py::arg("kh"), py::arg("split_blocks") = 0);
@@ -1221,7 +1064,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "rmsnorm + quantize + fp8 gate_up GEMV + SwiGLU, one launch");
   m.def("quant_fp8", &quant_fp8, "rowwise bf16 -> e4m3 quantizer");
   m.def("mfma_rate", &mfma_rate, "MFMA issue-rate microbench (bf16/fp8)");
-  m.def("rope_inplace_ds", &rope_inplace_ds, "graph-mode RoPE (device pos)");
   m.def("rope_kv", &rope_kv, "fused RoPE + paged KV scatter",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cost"),
         py::arg("sint"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
@@ -1238,13 +1080,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("out"), py::arg("cost"), py::arg("sint"), py::arg("kc"),
         py::arg("vc"), py::arg("page_table"), py::arg("pos0"), py::arg("hq"),
         py::arg("kh"), py::arg("pos_state") = py::none());
-  m.def("kv_write_ds", &kv_write_ds, "graph-mode KV scatter (device pos)");
-  m.def("attn_decode_paged_ds", &attn_decode_paged_ds,
-        "graph-mode paged decode attention (device pos)",
-        py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
-        py::arg("pos_state"), py::arg("max_seq"), py::arg("scale"),
-        py::arg("out") = py::none(), py::arg("identity") = false,
-        py::arg("split_blocks") = 0);
   m.def("sample_state", &sample_state, "graph-mode on-device sampling");
   m.def("bump", &bump, "graph-mode pos/step bump");
   m.def("rope_kv_fp8", &rope_kv_fp8,
@@ -1261,14 +1096,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "paged decode attention over an fp8 KV cache",
         py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("ksc"),
         py::arg("vsc"), py::arg("page_table"), py::arg("seq_len"),
-        py::arg("scale"), py::arg("identity") = false,
+        py::arg("scale"), py::arg("pos_state") = py::none(),
+        py::arg("out") = py::none(), py::arg("identity") = false,
         py::arg("split_blocks") = 0);
-  m.def("attn_decode_paged_fp8_ds", &attn_decode_paged_fp8_ds,
-        "graph-mode paged decode attention over an fp8 KV cache",
-        py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("ksc"),
-        py::arg("vsc"), py::arg("page_table"), py::arg("pos_state"),
-        py::arg("max_seq"), py::arg("scale"), py::arg("out") = py::none(),
-        py::arg("identity") = false, py::arg("split_blocks") = 0);
   m.def("ws_release", &ws_release,
         "drop decode-attention scratch for a dead KV cache");
 }

@@ -10,6 +10,7 @@
 //  - all kernels are grid-stride free (static shapes from the caller).
 
 #include "common.h"
+#include "launchers.h"
 
 // ---------------------------------------------------------------------------
 // RMSNorm: y[r,:] = x[r,:] / rms * w.  One 256-thread block per row.
@@ -256,4 +257,72 @@ kv_write_kernel(const ushort_t *__restrict__ k, const ushort_t *__restrict__ v,
     kd[i] = ks[i];
     vd[i] = vs[i];
   }
+}
+
+// ---------------------------------------------------------------------------
+// C-linkage launch wrappers: the block-size rules live here, next to the
+// kernels whose indexing depends on them.
+// ---------------------------------------------------------------------------
+
+// decode-sized calls (1-4 rows): a single 256-thread block is latency-bound
+// under a loaded memory system (rocprof: 12.6 us avg at 3-opponent
+// concurrency) — 4x the threads quarters the serial depth
+static inline int norm_block_threads(int t) { return t <= 4 ? 1024 : 256; }
+
+extern "C" void launch_rmsnorm(const ushort_t *x, const ushort_t *w,
+                               ushort_t *y, int t, int d, float eps,
+                               hipStream_t stream) {
+  rmsnorm_kernel<<<t, norm_block_threads(t), 0, stream>>>(x, w, y, d, eps);
+}
+
+extern "C" void launch_add_rmsnorm(const ushort_t *resid,
+                                   const ushort_t *delta, const ushort_t *w,
+                                   ushort_t *resid_out, ushort_t *y, int t,
+                                   int d, float eps, hipStream_t stream) {
+  add_rmsnorm_kernel<<<t, norm_block_threads(t), 0, stream>>>(
+      resid, delta, w, resid_out, y, d, eps);
+}
+
+extern "C" void launch_rope(ushort_t *q, ushort_t *k, const float *cost,
+                            const float *sint, int t, int hq, int hk, int hd,
+                            int pos0, long q_rstride, long k_rstride,
+                            const int *pos_ptr, hipStream_t stream) {
+  const int waves = t * (hq + hk);  // one wave per (token, head)
+  const int blocks = (waves * 64 + 255) / 256;
+  rope_kernel<<<blocks, 256, 0, stream>>>(q, k, cost, sint, t, hq, hk, hd,
+                                          pos0, q_rstride, k_rstride, pos_ptr);
+}
+
+extern "C" void launch_rope_kv(ushort_t *q, ushort_t *k, const ushort_t *v,
+                               const float *cost, const float *sint,
+                               ushort_t *kc, ushort_t *vc,
+                               const int *page_table, int t, int hq, int hk,
+                               int hd, int pos0, long q_rstride,
+                               long k_rstride, long v_rstride, int page,
+                               const int *pos_ptr, hipStream_t stream) {
+  const int waves = t * (hq + 2 * hk);  // one wave per (token, slot)
+  const int thr = rope_kv_block_threads(t);
+  const int blocks = (waves * 64 + thr - 1) / thr;
+  rope_kv_kernel<<<blocks, thr, 0, stream>>>(
+      q, k, v, cost, sint, kc, vc, page_table, t, hq, hk, hd, pos0, q_rstride,
+      k_rstride, v_rstride, page, pos_ptr);
+}
+
+extern "C" void launch_swiglu(const ushort_t *gate, const ushort_t *up,
+                              ushort_t *out, int t, int f, int in_stride,
+                              hipStream_t stream) {
+  const long nvec = (long)t * f / 8;
+  long blocks = (nvec + 255) / 256;  // the kernel grid-strides past the cap
+  if (blocks > 8192) blocks = 8192;
+  swiglu_kernel<<<(int)blocks, 256, 0, stream>>>(gate, up, out, t, f,
+                                                 in_stride);
+}
+
+extern "C" void launch_kv_write(const ushort_t *k, const ushort_t *v,
+                                ushort_t *kc, ushort_t *vc,
+                                const int *page_table, int pos0, int t, int kh,
+                                int hd, int page, const int *pos_ptr,
+                                hipStream_t stream) {
+  kv_write_kernel<<<t, 256, 0, stream>>>(k, v, kc, vc, page_table, pos0, t, kh,
+                                         hd, page, pos_ptr);  // block = token
 }

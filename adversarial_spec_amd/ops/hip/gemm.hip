@@ -25,6 +25,7 @@
 // path into the same swizzled image, so the MFMA loop is shared.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8v;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;

@@ -44,6 +44,7 @@
 // (bindings.hip gemm()) falls back to gemm.hip otherwise.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8v;
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;

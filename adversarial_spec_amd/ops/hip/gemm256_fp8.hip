@@ -21,6 +21,7 @@
 // Fragments are 8-B reads of the low/high half of a swizzled chunk.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;
 

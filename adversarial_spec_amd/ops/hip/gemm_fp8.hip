@@ -15,6 +15,7 @@
 // 8 fp8 = 8 B per lane read as the low/high half of a swizzled 16 B chunk.
 
 #include "common.h"
+#include "launchers.h"
 #include "rope_epilogue.h"
 
 typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;
@@ -451,14 +452,13 @@ gemv_fp8_rope_kv_w32_kernel(const uint8_t *__restrict__ x,
   rope_kv_store(pre, y, n_even, acc * xs[0] * ws_n, lane);
 }
 
-extern "C" void launch_gemv_fp8_rope_kv(
-    const uint8_t *x, const float *xs, const uint8_t *w, const float *wsc,
-    ushort_t *y, int K, const float *cost, const float *sint, ushort_t *kc,
-    ushort_t *vc, const int *page_table, const int *pos_ptr, int pos, int hq,
-    int kh, int hd, int page, hipStream_t stream) {
-  const int N = (hq + 2 * kh) * hd;  // caller checked: hd % 16 == 0, N <= 8192
-  const RopeKvArgs ra = {cost, sint, kc, vc, page_table, pos_ptr,
-                         pos,  hq,   kh, hd, page};
+extern "C" void launch_gemv_fp8_rope_kv(const uint8_t *x, const float *xs,
+                                        const uint8_t *w, const float *wsc,
+                                        ushort_t *y, int K,
+                                        const RopeKvArgs &ra,
+                                        hipStream_t stream) {
+  // caller checked: hd % 16 == 0, N <= 8192
+  const int N = (ra.hq + 2 * ra.kh) * ra.hd;
   gemv_fp8_rope_kv_w32_kernel<<<dim3(N / 8), 256, 0, stream>>>(x, xs, w, wsc,
                                                                y, K, ra);
 }

@@ -14,6 +14,7 @@
 // slowdown in round 1).
 
 #include "common.h"
+#include "launchers.h"
 #include "rope_epilogue.h"
 // dot8_bf16 (packed v_dot2_f32_bf16 row dot) comes from common.h
 
@@ -442,14 +443,13 @@ extern "C" void launch_gemv_norm(const ushort_t *x, const ushort_t *wln,
                                                                 K, N, eps);
 }
 
-extern "C" void launch_gemv_norm_rope_kv(
-    const ushort_t *x, const ushort_t *wln, const ushort_t *w, ushort_t *y,
-    int K, float eps, const float *cost, const float *sint, ushort_t *kc,
-    ushort_t *vc, const int *page_table, const int *pos_ptr, int pos, int hq,
-    int kh, int hd, int page, hipStream_t stream) {
-  const int N = (hq + 2 * kh) * hd;  // caller checked: hd % 16 == 0, N <= 8192
-  const RopeKvArgs ra = {cost, sint, kc, vc, page_table, pos_ptr,
-                         pos,  hq,   kh, hd, page};
+extern "C" void launch_gemv_norm_rope_kv(const ushort_t *x,
+                                         const ushort_t *wln,
+                                         const ushort_t *w, ushort_t *y, int K,
+                                         float eps, const RopeKvArgs &ra,
+                                         hipStream_t stream) {
+  // caller checked: hd % 16 == 0, N <= 8192
+  const int N = (ra.hq + 2 * ra.kh) * ra.hd;
   gemv_norm_rope_kv_w32_kernel<<<dim3(N / 8), 256, (size_t)K * 2, stream>>>(
       x, wln, w, y, K, eps, ra);
 }

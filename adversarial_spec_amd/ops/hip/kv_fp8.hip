@@ -19,6 +19,7 @@
 // hd in {32, 64, 128}; group = hq/kh <= 8.
 
 #include "common.h"
+#include "launchers.h"
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 // 16-byte LDS reads go through a plain vector type: a ds_read of a struct
@@ -484,53 +485,50 @@ __global__ void __launch_bounds__(256) attn_decode_split_fp8_kernel(
   }
 }
 
-// defined in attention.hip; shared unchanged
-extern "C" __global__ void attn_decode_combine_kernel(const float *,
-                                                      const float *,
-                                                      const float *,
-                                                      ushort_t *, int, int,
-                                                      int);
-
 // ---------------------------------------------------------------------------
 // C-linkage launch wrappers
 // ---------------------------------------------------------------------------
 
-extern "C" void launch_attn_decode_split_fp8(
-    const ushort_t *q, const uint8_t *kc, const uint8_t *vc, const float *ksc,
-    const float *vsc, const int *page_table, int seq_len, float scale, int kh,
-    int group, int hd, int page, int split_len, int n_splits, float *ws_m,
-    float *ws_l, float *ws_acc, const int *pos_ptr, ushort_t *out,
-    int identity, hipStream_t stream) {
-  dim3 grid(kh, n_splits);
+extern "C" void launch_attn_decode_split_fp8(const ushort_t *q,
+                                             const uint8_t *kc,
+                                             const uint8_t *vc,
+                                             const float *ksc,
+                                             const float *vsc,
+                                             const DecodeSplitArgs &a,
+                                             ushort_t *out,
+                                             hipStream_t stream) {
+  dim3 grid(a.kh, a.n_splits);
 #define DISPATCH_ONE(HD, MG)                                                   \
   do {                                                                         \
-    if (identity)                                                              \
+    if (a.identity)                                                            \
       attn_decode_split_fp8_kernel<HD, MG, true><<<grid, 256, 0, stream>>>(    \
-          q, kc, vc, ksc, vsc, page_table, seq_len, scale, kh, group, page,    \
-          split_len, ws_m, ws_l, ws_acc, pos_ptr, out);                        \
+          q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,         \
+          a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,   \
+          out);                                                                \
     else                                                                       \
       attn_decode_split_fp8_kernel<HD, MG, false><<<grid, 256, 0, stream>>>(   \
-          q, kc, vc, ksc, vsc, page_table, seq_len, scale, kh, group, page,    \
-          split_len, ws_m, ws_l, ws_acc, pos_ptr, out);                        \
+          q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,         \
+          a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,   \
+          out);                                                                \
   } while (0)
 #define DISPATCH_MG(HD)                                                        \
   do {                                                                         \
-    if (group <= 2) DISPATCH_ONE(HD, 2);                                       \
-    else if (group <= 4) DISPATCH_ONE(HD, 4);                                  \
+    if (a.group <= 2) DISPATCH_ONE(HD, 2);                                     \
+    else if (a.group <= 4) DISPATCH_ONE(HD, 4);                                \
     else DISPATCH_ONE(HD, 8);                                                  \
   } while (0)
 
-  switch (hd) {
+  switch (a.hd) {
     case 32: DISPATCH_MG(32); break;
     case 64: DISPATCH_MG(64); break;
     case 128: DISPATCH_MG(128); break;
   }
 #undef DISPATCH_MG
 #undef DISPATCH_ONE
-  if (n_splits > 1) {
-    attn_decode_combine_kernel<<<dim3(kh * group, (hd + 63) / 64), 256, 0,
-                                 stream>>>(ws_m, ws_l, ws_acc, out, n_splits,
-                                           group, hd);
+  if (a.n_splits > 1) {
+    // the bf16 path's combine pass (attention.hip), shared unchanged
+    launch_attn_decode_combine(a.ws_m, a.ws_l, a.ws_acc, out, a.n_splits,
+                               a.kh, a.group, a.hd, stream);
   }
 }
 
@@ -541,9 +539,7 @@ extern "C" void launch_rope_kv_fp8(
     long q_rstride, long k_rstride, long v_rstride, int page,
     const int *pos_ptr, hipStream_t stream) {
   const int waves = t * (hq + 2 * hk);
-  // decode (t <= 2): one wave per block spreads the latency-bound
-  // slot-waves over more CUs, as rope_kv does
-  const int thr = t <= 2 ? 64 : 256;
+  const int thr = rope_kv_block_threads(t);  // shared with rope_kv
   const int blocks = (waves * 64 + thr - 1) / thr;
   rope_kv_fp8_kernel<<<blocks, thr, 0, stream>>>(
       q, k, v, cost, sint, kc, vc, ksc, vsc, page_table, t, hq, hk, hd, pos0,

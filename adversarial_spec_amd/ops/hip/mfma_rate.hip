@@ -13,6 +13,7 @@
 // kernel is pure matrix-pipe issue (no memory in the loop).
 
 #include "common.h"
+#include "launchers.h"
 
 typedef __attribute__((__vector_size__(8 * sizeof(short)))) short bf16x8v;
 typedef __attribute__((__vector_size__(2 * sizeof(int)))) int i32x2v;

@@ -15,15 +15,7 @@
 #pragma once
 
 #include "common.h"
-
-struct RopeKvArgs {
-  const float *cost, *sint;  // [max_pos, hd/2] f32
-  ushort_t *kc, *vc;         // [n_pages, page, kh, hd] bf16, contiguous
-  const int *page_table;
-  const int *pos_ptr;        // graph mode: device position word (else null)
-  int pos;                   // scalar position when pos_ptr is null
-  int hq, kh, hd, page;
-};
+#include "launchers.h"  // RopeKvArgs: the launchers take it, the kernels too
 
 struct RopeKvPre {
   float c, s;          // this pair's cos/sin at pos

@@ -16,6 +16,7 @@
 // greedy path (reference defaults 0.7 / 0.3: models.py:626).
 
 #include "common.h"
+#include "launchers.h"
 
 // logits: [vocab] bf16, vocab % 8 == 0. temp <= 0 -> greedy. Returns the
 // sampled id in *out; shared body for the plain and graph-state kernels.
@@ -115,4 +116,29 @@ extern "C" __global__ void bump_kernel(int *__restrict__ pos_state,
     pos_state[0] += 1;
     step_state[0] += 1;
   }
+}
+
+// ---------------------------------------------------------------------------
+// C-linkage launch wrappers. The samplers are single-block: sample_body
+// reduces the whole vocab inside one 1024-thread block.
+// ---------------------------------------------------------------------------
+
+extern "C" void launch_sample(const ushort_t *logits, int vocab, float temp,
+                              uint32_t seed, int *out, hipStream_t stream) {
+  sample_kernel<<<1, 1024, 0, stream>>>(logits, vocab, temp, seed, out);
+}
+
+extern "C" void launch_sample_state(const ushort_t *logits, int vocab,
+                                    const float *temp_state,
+                                    uint32_t *rng_state, int *tok_hist,
+                                    const int *step_state, long long *tok_long,
+                                    hipStream_t stream) {
+  sample_state_kernel<<<1, 1024, 0, stream>>>(logits, vocab, temp_state,
+                                              rng_state, tok_hist, step_state,
+                                              tok_long);
+}
+
+extern "C" void launch_bump(int *pos_state, int *step_state,
+                            hipStream_t stream) {
+  bump_kernel<<<1, 64, 0, stream>>>(pos_state, step_state);
 }

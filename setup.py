@@ -33,6 +33,12 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "sampling.hip"),
         os.path.join(HIP_DIR, "mfma_rate.hip"),
     ],
+    # headers are not sources: without this, editing one rebuilds nothing
+    depends=[
+        os.path.join(HIP_DIR, "launchers.h"),
+        os.path.join(HIP_DIR, "common.h"),
+        os.path.join(HIP_DIR, "rope_epilogue.h"),
+    ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
         "nvcc": ["-O3", "-std=c++17", "--offload-arch=gfx950"],

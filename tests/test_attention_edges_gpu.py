@@ -392,6 +392,76 @@ class TestDecodeMasking:
                        name=f"decode H graph s={seq} hd={hd}")
 
 
+class TestDecodeUnifiedEntry:
+    # K: host-length and device-position calls go through ONE entry with one
+    # set of argument checks. kh=2, hq=4, hd=32, page=16 over 4 pages at
+    # seq=17 is the smallest geometry that crosses a page boundary, so the
+    # page table is really walked. A refused call raises before anything is
+    # launched: the sentinel `out` it was handed stays untouched.
+    HD, GROUP, PAGE, SEQ = 32, 2, 16, 17
+
+    def _inputs(self):
+        q, kc, vc, table = _dev(*_decode_inputs(self.SEQ, self.HD, self.GROUP,
+                                                page=self.PAGE))
+        assert kc.shape == (4, self.PAGE, KH, self.HD) and q.shape[0] == 4
+        return q, kc, vc, table
+
+    def test_pos_state_bitwise_equals_host_length(self):
+        q, kc, vc, table = self._inputs()
+        host = ops.attn_decode_paged(q, kc, vc, table, self.SEQ)
+        dev = ops.attn_decode_paged(q, kc, vc, table, self.SEQ,
+                                    pos_state=_pos_state(self.SEQ - 1))
+        assert torch.equal(host, dev)
+        cpu = _decode_inputs(self.SEQ, self.HD, self.GROUP, page=self.PAGE)
+        _assert_within(host, ref_decode(*cpu, self.SEQ), **DECODE_TOL,
+                       name="decode K host")
+
+    def test_out_written_in_place_both_modes(self):
+        q, kc, vc, table = self._inputs()
+        want = ops.attn_decode_paged(q, kc, vc, table, self.SEQ)
+        for pos_state in (None, _pos_state(self.SEQ - 1)):
+            out = torch.full_like(want, 7.0)
+            ret = ops.attn_decode_paged(q, kc, vc, table, self.SEQ,
+                                        pos_state=pos_state, out=out)
+            assert ret.data_ptr() == out.data_ptr()
+            assert torch.equal(out, want)
+
+    @pytest.mark.parametrize("case", [
+        "pos_state int64", "pos_state on cpu", "float16 cache", "hq=3",
+        "hd=48", "out wrong shape", "seq_len past the cache",
+        "seq_len past the cache, graph mode",
+    ])
+    def test_refused_on_the_host(self, case):
+        q, kc, vc, table = self._inputs()
+        seq, kw = self.SEQ, {}
+        out = torch.full((4, self.HD), 7.0, dtype=torch.bfloat16, device=DEV)
+        if case == "pos_state int64":
+            kw["pos_state"] = torch.tensor([seq - 1], device=DEV)
+        elif case == "pos_state on cpu":
+            kw["pos_state"] = torch.tensor([seq - 1], dtype=torch.int32)
+        elif case == "float16 cache":
+            kc, vc = kc.to(torch.float16), vc.to(torch.float16)
+        elif case == "hq=3":
+            q, out = q[:3].contiguous(), out[:3].contiguous()
+        elif case == "hd=48":
+            q = _bf(torch.randn(4, 48)).to(DEV)
+            kc = _bf(torch.randn(4, self.PAGE, KH, 48)).to(DEV)
+            vc = kc.clone()
+            out = torch.full((4, 48), 7.0, dtype=torch.bfloat16, device=DEV)
+        elif case == "out wrong shape":
+            out = torch.full((4, self.HD + 8), 7.0, dtype=torch.bfloat16,
+                             device=DEV)
+        elif case == "seq_len past the cache":
+            seq = 4 * self.PAGE + 1
+        else:
+            seq = 4 * self.PAGE + 1
+            kw["pos_state"] = _pos_state(self.SEQ - 1)
+        with pytest.raises(RuntimeError):
+            ops.attn_decode_paged(q, kc, vc, table, seq, out=out, **kw)
+        torch.cuda.synchronize()
+        assert bool((out == 7.0).all()), f"{case}: out written despite refusal"
+
+
 # ---------------------------------------------------------------------------
 # prefill
 # ---------------------------------------------------------------------------

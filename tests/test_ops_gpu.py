@@ -285,6 +285,64 @@ class TestRopeKV:
         assert torch.equal(vc.cpu(), vc2.cpu())
 
 
+class TestPosStateEntries:
+    """kv_write and rope take the graph-mode device position through the same
+    entry as a host position: same bits at t=1, and a pos_state that is not a
+    device int32 word is refused on the host. kh=2, hq=4, hd=32, page=16 over
+    4 permuted pages; position 16 is the first row of the second page."""
+    HQ, KH, HD, PAGE, NPG, POS = 4, 2, 32, 16, 4, 16
+
+    def _cache(self):
+        kc = torch.zeros(self.NPG, self.PAGE, self.KH, self.HD,
+                         dtype=torch.bfloat16, device=DEV)
+        table = torch.tensor([2, 0, 3, 1], dtype=torch.int32, device=DEV)
+        return kc, torch.zeros_like(kc), table
+
+    def _pos_state(self, dtype=torch.int32, device=DEV):
+        return torch.tensor([self.POS], dtype=dtype, device=device)
+
+    def test_kv_write_matches_host_position(self):
+        k = _bf(torch.randn(1, self.KH, self.HD)).to(DEV)
+        v = _bf(torch.randn(1, self.KH, self.HD)).to(DEV)
+        kc, vc, table = self._cache()
+        kc2, vc2, _ = self._cache()
+        ops.kv_write(kc, vc, table, self.POS, k, v)
+        ops.kv_write(kc2, vc2, table, 0, k, v, pos_state=self._pos_state())
+        assert torch.equal(kc, kc2) and torch.equal(vc, vc2)
+        assert torch.equal(kc[0, 0], k[0]) and torch.equal(vc[0, 0], v[0])
+        assert int((kc != 0).sum()) == int((k != 0).sum())
+
+    def test_rope_matches_host_position(self):
+        cos, sin = torch_ref.rope_tables(self.HD, 64, 10000.0, DEV)
+        q = _bf(torch.randn(1, self.HQ, self.HD)).to(DEV)
+        k = _bf(torch.randn(1, self.KH, self.HD)).to(DEV)
+        q_ref, k_ref = torch_ref.rope(q.cpu(), k.cpu(), cos.cpu(), sin.cpu(),
+                                      self.POS)
+        q2, k2 = q.clone(), k.clone()
+        ops.rope(q, k, cos, sin, self.POS)
+        ops.rope(q2, k2, cos, sin, 0, pos_state=self._pos_state())
+        assert torch.equal(q, q2) and torch.equal(k, k2)
+        _assert_close(q, q_ref, atol=2e-2, name="rope q pos_state")
+        _assert_close(k, k_ref, atol=2e-2, name="rope k pos_state")
+
+    @pytest.mark.parametrize("bad", ["int64", "cpu"])
+    def test_bad_pos_state_refused(self, bad):
+        ps = (self._pos_state(dtype=torch.int64) if bad == "int64"
+              else self._pos_state(device="cpu"))
+        k = _bf(torch.randn(1, self.KH, self.HD)).to(DEV)
+        q = _bf(torch.randn(1, self.HQ, self.HD)).to(DEV)
+        kc, vc, table = self._cache()
+        cos, sin = torch_ref.rope_tables(self.HD, 64, 10000.0, DEV)
+        q0, k0 = q.clone(), k.clone()
+        with pytest.raises(RuntimeError):
+            ops.kv_write(kc, vc, table, 0, k, k, pos_state=ps)
+        with pytest.raises(RuntimeError):
+            ops.rope(q, k, cos, sin, 0, pos_state=ps)
+        torch.cuda.synchronize()
+        assert int((kc != 0).sum()) == 0 and int((vc != 0).sum()) == 0
+        assert torch.equal(q, q0) and torch.equal(k, k0)
+
+
 class TestGemm:
     # weights row-major [out, in]: C = a @ b^T (NT)
     @pytest.mark.parametrize("m", [3, 36, 56, 128, 300])
