@@ -779,13 +779,50 @@ torch::Tensor gemm_fp8(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc) {
   return c;
 }
 
+// Operands shared by the fp8 decode GEMVs, checked before any launch. The
+// kernels stream w8 and x8 in 16-byte chunks of 16 codes (nc = K / 16), so a
+// K that is no multiple of 16 would silently drop the row tails.
+static void check_fp8_weight(const char* who, const torch::Tensor& w8,
+                             const torch::Tensor& wsc) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 2 &&
+                  w8.is_contiguous(),
+              who, ": w8 contiguous uint8 [N, K] (e4m3fn bytes) on GPU");
+  TORCH_CHECK(w8.size(1) % 16 == 0, who, ": K % 16 == 0");
+  TORCH_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat &&
+                  wsc.is_contiguous() && wsc.numel() >= w8.size(0),
+              who, ": wsc contiguous f32, one scale per weight row, on GPU");
+}
+
+// The quantized activation: x8 holds at least K codes (the decode workspace
+// sizes it for the widest projection), xs[0] is its scale.
+static void check_fp8_act(const char* who, const torch::Tensor& x8,
+                          const torch::Tensor& xs, int64_t K) {
+  TORCH_CHECK(x8.is_cuda() && x8.scalar_type() == at::kByte &&
+                  x8.is_contiguous() && x8.numel() >= K,
+              who, ": x8 contiguous uint8 on GPU, numel >= K");
+  TORCH_CHECK(xs.is_cuda() && xs.scalar_type() == at::kFloat &&
+                  xs.numel() >= 1,
+              who, ": xs f32 on GPU, numel >= 1");
+}
+
+static void check_bf16_dst(const char* who, const torch::Tensor& dst,
+                           int64_t n) {
+  TORCH_CHECK(dst.is_cuda() && dst.scalar_type() == at::kBFloat16 &&
+                  dst.is_contiguous() && dst.numel() == n,
+              who, ": destination contiguous bf16 on GPU, one element per row");
+}
+
 // fp8 decode GEMV (allocation-free: caller provides the x8/xs scratch and
 // the output — all preallocated in the DecodeWorkspace for graph capture).
 void gemv_fp8(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc,
               torch::Tensor x8, torch::Tensor xs, torch::Tensor out) {
   CHECK_BF16_CUDA(x);
+  check_fp8_weight("gemv_fp8", w8, wsc);
+  const int N = w8.size(0), K = w8.size(1);
+  TORCH_CHECK((long)x.numel() == (long)K, "gemv_fp8: x numel == K");
+  check_fp8_act("gemv_fp8", x8, xs, K);
+  check_bf16_dst("gemv_fp8", out, N);
   auto xc = x.contiguous();
-  const int K = xc.numel(), N = w8.size(0);
   launch_quant_fp8(uptr(xc), x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                    1, K, cur_stream());
   launch_gemv_fp8(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
@@ -814,9 +851,10 @@ void quant_norm_fp8(torch::Tensor x, torch::Tensor wln, torch::Tensor x8,
 // pre-quantized fp8 GEMV (x8/xs from quant_norm_fp8): out = x8 @ w8^T
 void gemv_fp8_q(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
                 torch::Tensor wsc, torch::Tensor out) {
+  check_fp8_weight("gemv_fp8_q", w8, wsc);
   const int N = w8.size(0), K = w8.size(1);
-  TORCH_CHECK(x8.numel() >= K && x8.scalar_type() == at::kByte);
-  TORCH_CHECK((long)out.numel() == (long)N);
+  check_fp8_act("gemv_fp8_q", x8, xs, K);
+  check_bf16_dst("gemv_fp8_q", out, N);
   launch_gemv_fp8(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                   w8.data_ptr<uint8_t>(), wsc.data_ptr<float>(),
                   uptr_mut(out), K, N, cur_stream());
@@ -827,11 +865,13 @@ void gemv_fp8_q(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
 void gemv_fp8_res(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc,
                   torch::Tensor x8, torch::Tensor xs, torch::Tensor resid) {
   CHECK_BF16_CUDA(x);
-  CHECK_BF16_CUDA(resid);
-  auto xc = x.contiguous();
-  const int K = xc.numel(), N = w8.size(0);
-  TORCH_CHECK((long)resid.numel() == (long)N && resid.is_contiguous());
+  check_fp8_weight("gemv_fp8_res", w8, wsc);
+  const int N = w8.size(0), K = w8.size(1);
+  TORCH_CHECK((long)x.numel() == (long)K, "gemv_fp8_res: x numel == K");
+  check_fp8_act("gemv_fp8_res", x8, xs, K);
+  check_bf16_dst("gemv_fp8_res", resid, N);
   TORCH_CHECK(N <= 8192, "gemv_fp8_res: w32 kernel only (hidden <= 8192)");
+  auto xc = x.contiguous();
   launch_quant_fp8(uptr(xc), x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                    1, K, cur_stream());
   launch_gemv_fp8_res(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
@@ -842,10 +882,11 @@ void gemv_fp8_res(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc,
 // pre-quantized fused fp8 gate_up GEMV + SwiGLU
 void gemv_fp8_gateup(torch::Tensor x8, torch::Tensor xs, torch::Tensor w8,
                      torch::Tensor wsc, torch::Tensor act) {
-  CHECK_BF16_CUDA(act);
+  check_fp8_weight("gemv_fp8_gateup", w8, wsc);
   const int K = w8.size(1), F2 = w8.size(0);
-  TORCH_CHECK(F2 % 2 == 0 && x8.numel() >= K);
-  TORCH_CHECK((long)act.numel() == (long)(F2 / 2));
+  TORCH_CHECK(F2 % 2 == 0, "gemv_fp8_gateup: w8 = [gate rows | up rows]");
+  check_fp8_act("gemv_fp8_gateup", x8, xs, K);
+  check_bf16_dst("gemv_fp8_gateup", act, F2 / 2);
   launch_gemv_fp8_gateup(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                          w8.data_ptr<uint8_t>(), wsc.data_ptr<float>(),
                          uptr_mut(act), K, F2 / 2, cur_stream());

@@ -310,27 +310,14 @@ gemv_fp8_kernel(const uint8_t *__restrict__ x, const float *__restrict__ xs,
 // ---------------------------------------------------------------------------
 
 DEVINL uint8_t f32_to_fp8(float f) {
-  // round-to-nearest via float -> e4m3 with saturation to +-448
-  const uint32_t s = (__builtin_bit_cast(uint32_t, f) >> 31) & 1;
-  float a = fabsf(f);
-  if (a > 448.f) a = 448.f;
-  if (a < 0.0009765625f) {  // < 2^-10: rounds to 0 or smallest subnormal
-    const uint32_t m = (uint32_t)(a * 512.f + 0.5f);  // in units of 2^-9
-    return (uint8_t)((s << 7) | m);
-  }
-  int e;
-  float mant = frexpf(a, &e);        // a = mant * 2^e, mant in [0.5, 1)
-  // e4m3 value = (1.m3) * 2^(E-7): normalize to exponent e-1
-  int E = e - 1 + 7;
-  float mm = mant * 2.f;             // [1, 2)
-  int m3 = (int)((mm - 1.f) * 8.f + 0.5f);
-  if (m3 == 8) { m3 = 0; E += 1; }
-  if (E <= 0) {                      // subnormal
-    const uint32_t m = (uint32_t)(a * 512.f + 0.5f);
-    return (uint8_t)((s << 7) | (m > 7 ? 7 : m));
-  }
-  if (E > 15 || (E == 15 && m3 > 6)) { E = 15; m3 = 6; }  // clamp to 448
-  return (uint8_t)((s << 7) | (E << 3) | m3);
+  // float -> e4m3fn by the hardware packed convert (kv_fp8.hip uses the same
+  // one): round-to-nearest-even, subnormal-to-normal carry included, OCP
+  // encoding on gfx950. Saturates to +-448 in front of it, so a quotient
+  // that rounded a hair above 448 stays finite; a NaN passes both compares
+  // and converts to the e4m3fn NaN.
+  if (f > 448.f) f = 448.f;
+  if (f < -448.f) f = -448.f;
+  return (uint8_t)(__builtin_amdgcn_cvt_pk_fp8_f32(f, 0.f, 0, false) & 0xffu);
 }
 
 extern "C" __global__ void __launch_bounds__(256)

@@ -468,9 +468,18 @@ class TestFp8:
         assert torch.allclose(sc.cpu(), want_s, rtol=1e-5)
         got = q.cpu().view(torch.float8_e4m3fn).float()
         want = want_q.view(torch.float8_e4m3fn).float()
-        # RTNE boundary cases may differ by one ULP step
-        frac = (got != want).float().mean().item()
-        assert frac < 0.02, f"{frac*100:.2f}% mismatched codes"
+        # On scale-1 rows the kernel matches torch code for code
+        # (test_gemv_exact_gpu.py, every bf16 value). These rows are not
+        # scale-1: the kernel multiplies by inv = 1/scale where torch
+        # divides, one fp32 rounding more, which can only flip a quotient
+        # that lies within an fp32 ulp of an e4m3 midpoint: 32 midpoints
+        # among the 2^24 fp32 values of a binade, a ~2^-18 event per
+        # element. So among 2048 elements allow one, and only to the
+        # neighbouring code.
+        bad = got != want
+        assert int(bad.sum()) <= 1, f"{int(bad.sum())} mismatched codes"
+        step = (q.cpu().int() - want_q.int()).abs()
+        assert (step[bad] == 1).all()
 
     @pytest.mark.parametrize("m", [1, 36, 128, 300])
     def test_gemm_fp8_vs_dequant_ref(self, m):
