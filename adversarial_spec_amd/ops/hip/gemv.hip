@@ -14,52 +14,22 @@
 // slowdown in round 1).
 
 #include "common.h"
+#include "gemv_rows.h"
 #include "launchers.h"
 #include "rope_epilogue.h"
-// dot8_bf16 (packed v_dot2_f32_bf16 row dot) comes from common.h
+// dot8_bf16 (packed v_dot2_f32_bf16 row dot) comes from common.h; the loop
+// pair and the lane-group reduce are row_dot (gemv_rows.h)
 
-// 16-lane-group sum (lanes p, p+1, .., p+15 with stride 1)
-DEVINL float group16_sum(float v) {
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) v += __shfl_xor(v, off, WAVE);
-  return v;
-}
-
+// 16 lanes per row, 4-deep unroll (this kernel only runs at large N where
+// the grid itself saturates HBM; 8-deep measured slower there)
 extern "C" __global__ void __launch_bounds__(256)
 gemv_kernel(const ushort_t *__restrict__ x, const ushort_t *__restrict__ w,
             ushort_t *__restrict__ y, int K, int N) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 4;       // row group within wave: 0..3
-  const int sl = lane & 15;       // k-slice lane: 0..15
-  const int n = blockIdx.x * 16 + wid * 4 + rg;
-  if (n >= N) return;
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;           // 16 B chunks per row (K % 8 == 0)
-
-  float acc = 0.f;
-  int c = sl;
-  // 4-deep unroll (this kernel only runs at large N where the grid itself
-  // saturates HBM; 8-deep measured slower there)
-  for (; c + 48 < nc; c += 64) {
-    bf16x8 wv[4], xv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      wv[u] = ((const bf16x8 *)wr)[c + 16 * u];
-      xv[u] = ((const bf16x8 *)x)[c + 16 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) acc = dot8_bf16(xv[u], wv[u], acc);
-  }
-  for (; c < nc; c += 16) {
-    const bf16x8 wv = ((const bf16x8 *)wr)[c];
-    const bf16x8 xv = ((const bf16x8 *)x)[c];
-    acc = dot8_bf16(xv, wv, acc);
-  }
-
-  const float sum = group16_sum(acc);
-  if (sl == 0) y[n] = f32_to_bf16(sum);
+  const RowGeom<16> g;
+  if (g.n >= N) return;
+  const float acc =
+      row_dot<Bf16Row, 16, 4, X_GLOBAL>(x, w + (size_t)g.n * K, K, g.sl);
+  if (g.sl == 0) y[g.n] = f32_to_bf16(acc);
 }
 
 // 32-lanes-per-row variant for SMALL N (o/qkv-sized): the 16-lane kernel
@@ -68,37 +38,11 @@ gemv_kernel(const ushort_t *__restrict__ x, const ushort_t *__restrict__ w,
 extern "C" __global__ void __launch_bounds__(256)
 gemv_kernel_w32(const ushort_t *__restrict__ x, const ushort_t *__restrict__ w,
                 ushort_t *__restrict__ y, int K, int N) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;       // row group within wave: 0..1
-  const int sl = lane & 31;       // k-slice lane: 0..31
-  const int n = blockIdx.x * 8 + wid * 2 + rg;
-  if (n >= N) return;
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;
-
-  float acc = 0.f;
-  int c = sl;
-  for (; c + 224 < nc; c += 256) {
-    bf16x8 wv[8], xv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      wv[u] = ((const bf16x8 *)wr)[c + 32 * u];
-      xv[u] = ((const bf16x8 *)x)[c + 32 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = dot8_bf16(xv[u], wv[u], acc);
-  }
-  for (; c < nc; c += 32) {
-    const bf16x8 wv = ((const bf16x8 *)wr)[c];
-    const bf16x8 xv = ((const bf16x8 *)x)[c];
-    acc = dot8_bf16(xv, wv, acc);
-  }
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  if (sl == 0) y[n] = f32_to_bf16(acc);
+  const RowGeom<32> g;
+  if (g.n >= N) return;
+  const float acc =
+      row_dot<Bf16Row, 32, 8, X_GLOBAL>(x, w + (size_t)g.n * K, K, g.sl);
+  if (g.sl == 0) y[g.n] = f32_to_bf16(acc);
 }
 
 extern "C" void launch_gemv(const ushort_t *x, const ushort_t *w, ushort_t *y,
@@ -120,48 +64,13 @@ extern "C" __global__ void __launch_bounds__(256)
 gemv_gateup_kernel(const ushort_t *__restrict__ x,
                    const ushort_t *__restrict__ w,
                    ushort_t *__restrict__ act, int K, int F) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;       // row group within wave: 0..1
-  const int sl = lane & 31;       // k-slice lane: 0..31
-  const int n = blockIdx.x * 8 + wid * 2 + rg;
-  if (n >= F) return;
-
-  const ushort_t *wg = w + (size_t)n * K;
-  const ushort_t *wu = w + (size_t)(n + F) * K;
-  const int nc = K / 8;
-
-  float ag = 0.f, au = 0.f;
-  int c = sl;
-  for (; c + 96 < nc; c += 128) {
-    bf16x8 gv[4], uv[4], xv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      gv[u] = ((const bf16x8 *)wg)[c + 32 * u];
-      uv[u] = ((const bf16x8 *)wu)[c + 32 * u];
-      xv[u] = ((const bf16x8 *)x)[c + 32 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      ag = dot8_bf16(xv[u], gv[u], ag);
-      au = dot8_bf16(xv[u], uv[u], au);
-    }
-  }
-  for (; c < nc; c += 32) {
-    const bf16x8 xv = ((const bf16x8 *)x)[c];
-    ag = dot8_bf16(xv, ((const bf16x8 *)wg)[c], ag);
-    au = dot8_bf16(xv, ((const bf16x8 *)wu)[c], au);
-  }
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) {
-    ag += __shfl_xor(ag, off, WAVE);
-    au += __shfl_xor(au, off, WAVE);
-  }
-  if (sl == 0) {
-    const float s = ag / (1.0f + __expf(-ag));  // silu(gate)
-    act[n] = f32_to_bf16(s * au);
-  }
+  const RowGeom<32> g;
+  if (g.n >= F) return;
+  const ushort_t *const gu[2] = {w + (size_t)g.n * K,
+                                 w + (size_t)(g.n + F) * K};
+  float a[2];  // gate, up
+  row_dot<Bf16Row, 32, 4, X_GLOBAL>(x, gu, K, g.sl, a);
+  if (g.sl == 0) act[g.n] = f32_to_bf16(silu_mul(a[0], a[1]));
 }
 
 extern "C" void launch_gemv_gateup(const ushort_t *x, const ushort_t *w,
@@ -225,34 +134,13 @@ gemv_norm_w32_kernel(const ushort_t *__restrict__ x,
                      ushort_t *__restrict__ y, int K, int N, float eps) {
   extern __shared__ ushort_t xl[];  // K bf16: x*wln (unnormalized)
   __shared__ float red[16];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;
-  const int sl = lane & 31;
-  const int n0 = blockIdx.x * 8 + wid * 2 + rg;
+  const RowGeom<32> g;
   // no early return before the barrier: clamp the row, guard the write
-  const int n = n0 < N ? n0 : N - 1;
-
+  const int n = g.n < N ? g.n : N - 1;
   const float rms = norm_stage_lds(x, wln, xl, red, K, eps);
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;
-  float acc = 0.f;
-  int c = sl;
-  for (; c + 224 < nc; c += 256) {
-    bf16x8 wv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) wv[u] = ((const bf16x8 *)wr)[c + 32 * u];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      acc = dot8_bf16(((const bf16x8 *)xl)[c + 32 * u], wv[u], acc);
-  }
-  for (; c < nc; c += 32)
-    acc = dot8_bf16(((const bf16x8 *)xl)[c], ((const bf16x8 *)wr)[c], acc);
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  if (sl == 0 && n0 < N) y[n0] = f32_to_bf16(acc * rms);
+  const float acc =
+      row_dot<Bf16Row, 32, 8, X_LDS>(xl, w + (size_t)n * K, K, g.sl);
+  if (g.sl == 0 && g.n < N) y[g.n] = f32_to_bf16(acc * rms);
 }
 
 // qkv projection + RoPE + KV append in ONE launch: gemv_norm_w32_kernel's
@@ -269,36 +157,13 @@ gemv_norm_rope_kv_w32_kernel(const ushort_t *__restrict__ x,
                              RopeKvArgs ra) {
   extern __shared__ ushort_t xl[];  // K bf16: x*wln (unnormalized)
   __shared__ float red[16];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;
-  const int sl = lane & 31;
-  const int n_even = blockIdx.x * 8 + wid * 2;
-  const int n = n_even + rg;
-
+  const RowGeom<32> g;
   // epilogue operands first: their latency hides under prologue + stream
-  const RopeKvPre pre = rope_kv_prefetch(ra, n_even);
-
+  const RopeKvPre pre = rope_kv_prefetch(ra, g.n_even);
   const float rms = norm_stage_lds(x, wln, xl, red, K, eps);
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;
-  float acc = 0.f;
-  int c = sl;
-  for (; c + 224 < nc; c += 256) {
-    bf16x8 wv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) wv[u] = ((const bf16x8 *)wr)[c + 32 * u];
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      acc = dot8_bf16(((const bf16x8 *)xl)[c + 32 * u], wv[u], acc);
-  }
-  for (; c < nc; c += 32)
-    acc = dot8_bf16(((const bf16x8 *)xl)[c], ((const bf16x8 *)wr)[c], acc);
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  rope_kv_store(pre, y, n_even, acc * rms, lane);
+  const float acc =
+      row_dot<Bf16Row, 32, 8, X_LDS>(xl, w + (size_t)g.n * K, K, g.sl);
+  rope_kv_store(pre, y, g.n_even, acc * rms, g.lane);
 }
 
 // 16-lane-group norm variant for LARGE N (lm_head: final_norm fused)
@@ -309,33 +174,12 @@ gemv_norm_kernel(const ushort_t *__restrict__ x,
                  ushort_t *__restrict__ y, int K, int N, float eps) {
   extern __shared__ ushort_t xl[];
   __shared__ float red[16];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 4;
-  const int sl = lane & 15;
-  const int n0 = blockIdx.x * 16 + wid * 4 + rg;
-  const int n = n0 < N ? n0 : N - 1;
-
+  const RowGeom<16> g;
+  const int n = g.n < N ? g.n : N - 1;
   const float rms = norm_stage_lds(x, wln, xl, red, K, eps);
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;
-  float acc = 0.f;
-  int c = sl;
-  for (; c + 48 < nc; c += 64) {
-    bf16x8 wv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) wv[u] = ((const bf16x8 *)wr)[c + 16 * u];
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      acc = dot8_bf16(((const bf16x8 *)xl)[c + 16 * u], wv[u], acc);
-  }
-  for (; c < nc; c += 16)
-    acc = dot8_bf16(((const bf16x8 *)xl)[c], ((const bf16x8 *)wr)[c], acc);
-
-#pragma unroll
-  for (int off = 8; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  if (sl == 0 && n0 < N) y[n0] = f32_to_bf16(acc * rms);
+  const float acc =
+      row_dot<Bf16Row, 16, 4, X_LDS>(xl, w + (size_t)n * K, K, g.sl);
+  if (g.sl == 0 && g.n < N) y[g.n] = f32_to_bf16(acc * rms);
 }
 
 // residual-add epilogue variant: resid[n] += x @ W[n] (in place).
@@ -343,37 +187,14 @@ extern "C" __global__ void __launch_bounds__(256)
 gemv_res_w32_kernel(const ushort_t *__restrict__ x,
                     const ushort_t *__restrict__ w,
                     ushort_t *__restrict__ resid, int K, int N) {
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;
-  const int sl = lane & 31;
-  const int n = blockIdx.x * 8 + wid * 2 + rg;
-  if (n >= N) return;
-
-  const ushort_t *wr = w + (size_t)n * K;
-  const int nc = K / 8;
+  const RowGeom<32> g;
+  if (g.n >= N) return;
   // prefetch the residual word now: a dependent load AFTER the dot loop
   // adds its full latency to the kernel tail (probe: +0.25 us/launch)
-  const float r0 = bf16_to_f32(resid[n]);
-
-  float acc = 0.f;
-  int c = sl;
-  for (; c + 224 < nc; c += 256) {
-    bf16x8 wv[8], xv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      wv[u] = ((const bf16x8 *)wr)[c + 32 * u];
-      xv[u] = ((const bf16x8 *)x)[c + 32 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc = dot8_bf16(xv[u], wv[u], acc);
-  }
-  for (; c < nc; c += 32)
-    acc = dot8_bf16(((const bf16x8 *)x)[c], ((const bf16x8 *)wr)[c], acc);
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) acc += __shfl_xor(acc, off, WAVE);
-  if (sl == 0) resid[n] = f32_to_bf16(r0 + acc);
+  const float r0 = bf16_to_f32(resid[g.n]);
+  const float acc =
+      row_dot<Bf16Row, 32, 8, X_GLOBAL>(x, w + (size_t)g.n * K, K, g.sl);
+  if (g.sl == 0) resid[g.n] = f32_to_bf16(r0 + acc);
 }
 
 extern "C" __global__ void __launch_bounds__(256)
@@ -383,51 +204,14 @@ gemv_gateup_norm_kernel(const ushort_t *__restrict__ x,
                         ushort_t *__restrict__ act, int K, int F, float eps) {
   extern __shared__ ushort_t xl[];
   __shared__ float red[16];
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int rg = lane >> 5;
-  const int sl = lane & 31;
-  const int n0 = blockIdx.x * 8 + wid * 2 + rg;
-  const int n = n0 < F ? n0 : F - 1;
-
+  const RowGeom<32> g;
+  const int n = g.n < F ? g.n : F - 1;
   const float rms = norm_stage_lds(x, wln, xl, red, K, eps);
-
-  const ushort_t *wg = w + (size_t)n * K;
-  const ushort_t *wu = w + (size_t)(n + F) * K;
-  const int nc = K / 8;
-
-  float ag = 0.f, au = 0.f;
-  int c = sl;
-  for (; c + 96 < nc; c += 128) {
-    bf16x8 gv[4], uv[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      gv[u] = ((const bf16x8 *)wg)[c + 32 * u];
-      uv[u] = ((const bf16x8 *)wu)[c + 32 * u];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const bf16x8 xv = ((const bf16x8 *)xl)[c + 32 * u];
-      ag = dot8_bf16(xv, gv[u], ag);
-      au = dot8_bf16(xv, uv[u], au);
-    }
-  }
-  for (; c < nc; c += 32) {
-    const bf16x8 xv = ((const bf16x8 *)xl)[c];
-    ag = dot8_bf16(xv, ((const bf16x8 *)wg)[c], ag);
-    au = dot8_bf16(xv, ((const bf16x8 *)wu)[c], au);
-  }
-
-#pragma unroll
-  for (int off = 16; off > 0; off >>= 1) {
-    ag += __shfl_xor(ag, off, WAVE);
-    au += __shfl_xor(au, off, WAVE);
-  }
-  if (sl == 0 && n0 < F) {
-    const float g = ag * rms;
-    const float s = g / (1.0f + __expf(-g));  // silu(gate)
-    act[n0] = f32_to_bf16(s * (au * rms));
-  }
+  const ushort_t *const gu[2] = {w + (size_t)n * K, w + (size_t)(n + F) * K};
+  float a[2];  // gate, up
+  row_dot<Bf16Row, 32, 4, X_LDS>(xl, gu, K, g.sl, a);
+  if (g.sl == 0 && g.n < F)
+    act[g.n] = f32_to_bf16(silu_mul(a[0] * rms, a[1] * rms));
 }
 
 extern "C" void launch_gemv_norm(const ushort_t *x, const ushort_t *wln,

@@ -174,6 +174,8 @@ void launch_gemm_fp8(const uint8_t *a, const float *asc, const uint8_t *b,
 void launch_gemm_fp8_256(const uint8_t *a, const float *asc, const uint8_t *b,
                          const float *bsc, ushort_t *c, int M, int N, int K,
                          hipStream_t stream);
+
+// ---- gemv_fp8.hip: e4m3 decode GEMVs and activation quantizers ------------
 // x [M, K] bf16 -> q [M, K] e4m3, scale [M]
 void launch_quant_fp8(const ushort_t *x, uint8_t *q, float *scale, int M,
                       int K, hipStream_t stream);

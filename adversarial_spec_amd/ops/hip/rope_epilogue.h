@@ -1,5 +1,5 @@
 // RoPE + paged KV append as the epilogue of the w32 decode GEMVs
-// (gemv.hip bf16, gemm_fp8.hip fp8).
+// (gemv.hip bf16, gemv_fp8.hip fp8).
 //
 // In the w32 geometry wave `wid` of a block owns output rows
 // blockIdx.x*8 + wid*2 + {0,1}: lanes 0..31 reduce the even row, lanes

@@ -26,6 +26,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "attn_prefill_mfma.hip"),
         os.path.join(HIP_DIR, "kv_fp8.hip"),
         os.path.join(HIP_DIR, "gemv.hip"),
+        os.path.join(HIP_DIR, "gemv_fp8.hip"),
         os.path.join(HIP_DIR, "gemm.hip"),
         os.path.join(HIP_DIR, "gemm256.hip"),
         os.path.join(HIP_DIR, "gemm_fp8.hip"),
@@ -38,6 +39,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "launchers.h"),
         os.path.join(HIP_DIR, "common.h"),
         os.path.join(HIP_DIR, "rope_epilogue.h"),
+        os.path.join(HIP_DIR, "gemv_rows.h"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

@@ -12,7 +12,7 @@ F8 = torch.float8_e4m3fn
 
 # (L lanes per row, U unroll depth, E elements per 16-byte chunk) of every
 # decode GEMV kernel. This mirrors the loop pair each kernel in
-# ops/hip/gemv.hip and ops/hip/gemm_fp8.hip runs per lane, with nc = K / E
+# ops/hip/gemv.hip and ops/hip/gemv_fp8.hip runs per lane, with nc = K / E
 # and c starting at the lane's index sl in [0, L):
 #     for (; c + (U - 1) * L < nc; c += U * L)   // unrolled
 #     for (; c < nc; c += L)                     // remainder
@@ -27,7 +27,7 @@ KERNELS = {
     "gemv_norm_rope_kv_w32_kernel": (32, 8, 8),
     "gemv_res_w32_kernel": (32, 8, 8),
     "gemv_gateup_norm_kernel": (32, 4, 8),
-    # gemm_fp8.hip (e4m3, 16 elements per chunk)
+    # gemv_fp8.hip (e4m3, 16 elements per chunk)
     "gemv_fp8_kernel_w32": (32, 4, 16),
     "gemv_fp8_kernel": (16, 4, 16),
     "gemv_fp8_rope_kv_w32_kernel": (32, 4, 16),

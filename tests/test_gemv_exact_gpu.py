@@ -1,4 +1,4 @@
-"""Decode GEMV kernels (ops/hip/gemv.hip, ops/hip/gemm_fp8.hip) at their loop
+"""Decode GEMV kernels (ops/hip/gemv.hip, ops/hip/gemv_fp8.hip) at their loop
 tails and row edges, without a numeric tolerance.
 
   - Inputs built from small integers make every fp32 product and partial sum
