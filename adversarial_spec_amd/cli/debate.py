@@ -50,6 +50,22 @@ ACTIONS = [
 ]
 
 
+def _top_p_arg(text: str) -> float:
+    """argparse type of --top-p: range-checked at parse time."""
+    try:
+        return providers.validate_sampling_filter(float(text), 0)[0]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
+def _top_k_arg(text: str) -> int:
+    """argparse type of --top-k: range-checked at parse time."""
+    try:
+        return providers.validate_sampling_filter(1.0, int(text))[1]
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="debate.py",
@@ -137,6 +153,12 @@ Bedrock:
                         help="KV-cache storage for `local alias` (fp8 = "
                              "rowwise e4m3 cache, half the KV bytes; "
                              "independent of --model-dtype)")
+    parser.add_argument("--top-p", type=_top_p_arg, default=None,
+                        help="Default nucleus (top-p) sampling cut-off for "
+                             "`local alias`, 0 < p <= 1 (1 = off)")
+    parser.add_argument("--top-k", type=_top_k_arg, default=None,
+                        help="Default top-k sampling cut-off for `local "
+                             "alias`, integer >= 0 (0 = off)")
     # misc
     parser.add_argument("--timeout", type=int, default=600,
                         help="Timeout in seconds for model calls (default: 600)")
@@ -231,6 +253,7 @@ def handle_utility_command(args: argparse.Namespace) -> Optional[int]:
         return providers.handle_local_command(
             args.profile_name, args.bedrock_arg, args.extra_arg,
             args.weights, args.gpu, args.model_dtype, args.kv_dtype,
+            args.top_p, args.top_k,
         )
     return None
 

@@ -111,13 +111,22 @@ class LocalBackend:
         self.last_timings: dict[str, float] = {}
 
     def generate(self, system_prompt: str, user_message: str, *, max_tokens: int,
-                 temperature: float, timeout: float, top_p: float = 1.0, **_):
+                 temperature: float, timeout: float,
+                 top_p: Optional[float] = None, top_k: Optional[int] = None,
+                 **_):
         from .local import get_engine
 
         engine = get_engine(self.spec, device=self.device)
+        # forwarded only when the caller set them, so that the alias's own
+        # sampling defaults (spec keys top_p / top_k) apply otherwise
+        sampling = {}
+        if top_p is not None:
+            sampling["top_p"] = top_p
+        if top_k is not None:
+            sampling["top_k"] = top_k
         text, in_tok, out_tok, timings = engine.generate(
             system_prompt, user_message, max_tokens=max_tokens,
-            temperature=temperature, timeout=timeout, top_p=top_p,
+            temperature=temperature, timeout=timeout, **sampling,
         )
         self.last_timings = timings
         return text, in_tok, out_tok

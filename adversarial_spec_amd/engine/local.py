@@ -22,6 +22,7 @@ import torch
 from .. import ops
 from ..models import LlamaModel, get_config
 from ..models.llama import KV_DTYPES
+from ..providers import validate_sampling_filter
 from ..utils.timing import PhaseTimer
 from .tokenizer import build_tokenizer
 
@@ -74,6 +75,17 @@ def resolve_kv_dtype(spec: dict[str, Any]) -> str:
     return kv
 
 
+def resolve_sampling_filter(spec: dict[str, Any]) -> tuple[float, int]:
+    """An engine's default truncated-sampling setting: the optional spec keys
+    `top_p` (0 < top_p <= 1) and `top_k` (integer >= 0), falling back to
+    1.0 / 0, which is full-support sampling. Anything else is a
+    ValueError."""
+    top_p = spec.get("top_p")
+    top_k = spec.get("top_k")
+    return validate_sampling_filter(1.0 if top_p is None else top_p,
+                                    0 if top_k is None else top_k)
+
+
 def _seed_from_name(name: str) -> int:
     h = 2166136261
     for ch in name:
@@ -95,6 +107,8 @@ class LocalEngine:
                 device = "cpu"
         self.device = torch.device(device)
         self.kv_dtype = resolve_kv_dtype(spec)
+        # per-engine sampling defaults; generate(top_p=None / top_k=None)
+        self.top_p, self.top_k = resolve_sampling_filter(spec)
         self.model = LlamaModel(
             self.config, device=self.device, seed=_seed_from_name(self.name),
             tp=tp,
@@ -161,16 +175,26 @@ class LocalEngine:
         max_tokens: int = 8000,
         temperature: float = 0.7,
         timeout: float = 600.0,
-        top_p: float = 1.0,
+        top_p: Optional[float] = None,
+        top_k: Optional[int] = None,
     ) -> tuple[str, int, int, dict[str, float]]:
-        """Returns (text, input_tokens, output_tokens, phase timings ms)."""
+        """Returns (text, input_tokens, output_tokens, phase timings ms).
+
+        top_p / top_k truncate the sampling distribution (contract:
+        ops.torch_ref.nucleus_keep); None takes the engine's default, the
+        spec keys `top_p` / `top_k`, else 1.0 / 0 = no truncation. Out of
+        range (top_p outside (0, 1], top_k < 0) is a ValueError."""
+        top_p, top_k = validate_sampling_filter(
+            self.top_p if top_p is None else top_p,
+            self.top_k if top_k is None else top_k)
         with self._gen_lock:
             return self._generate_locked(
-                system_prompt, user_message, max_tokens, temperature, timeout, top_p
+                system_prompt, user_message, max_tokens, temperature, timeout,
+                top_p, top_k
             )
 
     def _generate_locked(self, system_prompt, user_message, max_tokens,
-                         temperature, timeout, top_p):
+                         temperature, timeout, top_p, top_k):
         deadline = time.monotonic() + timeout
         timer = PhaseTimer(sync_cuda=self.device.type == "cuda")
         ids = self.tokenizer.render_chat(system_prompt, user_message)
@@ -192,7 +216,8 @@ class LocalEngine:
             )
             with stream_ctx:
                 return self._generate_on_stream(
-                    ids, max_new, temperature, top_p, stop_ids, deadline, timer
+                    ids, max_new, temperature, top_p, top_k, stop_ids,
+                    deadline, timer
                 )
         finally:
             if prev_device is not None:
@@ -223,8 +248,8 @@ class LocalEngine:
         cache.seq_len = 0
         return cache
 
-    def _generate_on_stream(self, ids, max_new, temperature, top_p, stop_ids,
-                            deadline, timer):
+    def _generate_on_stream(self, ids, max_new, temperature, top_p, top_k,
+                            stop_ids, deadline, timer):
         # concurrency-aware attention split target (see _pick_split_blocks);
         # a change invalidates any captured graph (geometry is baked in)
         pick = self._pick_split_blocks()
@@ -251,9 +276,10 @@ class LocalEngine:
             # identically (deterministic kernel + identical all-reduced
             # activations), and the stop decision is rank-coordinated in
             # _decode_graphed so no rank leaves a collective early.
+            # Truncated sampling (top_p < 1 or top_k > 0) runs the same
+            # device-state loop with the filtered sampling kernel.
             use_async = (
                 self.device.type == "cuda"
-                and top_p >= 1.0
                 and ops.hip_available()
             )
             if use_async:
@@ -265,12 +291,12 @@ class LocalEngine:
                              and not os.environ.get("ADVSPEC_NO_GRAPH"))
                 out_ids = self._decode_graphed(
                     logits, cache, max_new, temperature, stop_ids, deadline,
-                    use_graph=use_graph,
+                    use_graph=use_graph, top_p=top_p, top_k=top_k,
                 )
             else:
                 out_ids = self._decode_sync(
-                    logits, cache, max_new, temperature, top_p, stop_ids,
-                    deadline,
+                    logits, cache, max_new, temperature, top_p, top_k,
+                    stop_ids, deadline,
                 )
 
         text = self.tokenizer.decode(out_ids)
@@ -282,16 +308,24 @@ class LocalEngine:
         ) & 0x7FFFFFFF
         return self._seed_counter
 
-    def _decode_sync(self, logits, cache, max_new, temperature, top_p,
+    def _decode_sync(self, logits, cache, max_new, temperature, top_p, top_k,
                      stop_ids, deadline) -> list[int]:
-        """Host-stepped decode (CPU path and nucleus sampling)."""
+        """Host-stepped decode (CPU devices, or no HIP extension)."""
         out_ids: list[int] = []
         scan = _StopScan(self.tokenizer)
+        filtered = top_p < 1.0 or top_k > 0
         for _ in range(max_new):
-            tok = ops.sample(
-                logits, temperature=temperature, top_p=top_p,
-                generator=self._sample_gen, seed=self._next_seed(),
-            )
+            if filtered:
+                tok = ops.sample_filtered(
+                    logits, temperature=temperature, top_p=top_p,
+                    top_k=top_k, generator=self._sample_gen,
+                    seed=self._next_seed(),
+                )
+            else:
+                tok = ops.sample(
+                    logits, temperature=temperature, top_p=top_p,
+                    generator=self._sample_gen, seed=self._next_seed(),
+                )
             if tok in stop_ids:
                 break
             out_ids.append(tok)
@@ -305,7 +339,8 @@ class LocalEngine:
         return out_ids
 
     def _decode_graphed(self, logits, cache, max_new, temperature, stop_ids,
-                        deadline, use_graph: bool = True) -> list[int]:
+                        deadline, use_graph: bool = True,
+                        top_p: float = 1.0, top_k: int = 0) -> list[int]:
         """Device-state decode loop; HIP-graph capture optional.
 
         The whole per-token step (sample -> n-layer forward -> logits copy
@@ -317,6 +352,15 @@ class LocalEngine:
         use_graph (ADVSPEC_NO_GRAPH, short generations) the SAME step runs
         eagerly, so both modes execute identical kernels with identical
         split geometry and produce bitwise-identical tokens.
+
+        Truncated sampling (top_p < 1 or top_k > 0) swaps the step's
+        sampling kernel for the filtered one, which reads top_p and top_k
+        from two more device words: their values change per request without
+        a recapture. Only the kernel choice, filtered or not, is part of the
+        graph key, so an engine that never truncates captures and replays
+        exactly the unfiltered graph. A request that flips that bit on a
+        warm engine recaptures, as cache growth does; the settings are
+        per-alias defaults, so that is rare.
         """
         from ..ops import _load_hip
 
@@ -336,7 +380,8 @@ class LocalEngine:
         # every request shape on a warm cache (rounds that alternate
         # max_new/temperature no longer recapture, and capture's device-wide
         # synchronize no longer stalls co-resident opponents per round).
-        key = (id(cache), cache.max_seq)
+        filtered = top_p < 1.0 or top_k > 0
+        key = (id(cache), cache.max_seq, filtered)
         if gs is not None and gs["key"] == key:
             # Round k+1 on a warm engine: reset the device-side state words
             # and replay the graph captured in round 1 — no re-capture.
@@ -351,6 +396,9 @@ class LocalEngine:
             step_state.zero_()
             rng_state.fill_(self._next_seed() | 1)
             temp_state.fill_(float(temperature))
+            if filtered:
+                gs["top_p_state"].fill_(float(top_p))
+                gs["top_k_state"].fill_(int(top_k))
             tok_hist.fill_(-1)
             W.tok_long.zero_()
             W.logits.copy_(logits.reshape(1, -1))
@@ -367,6 +415,12 @@ class LocalEngine:
             # slack: multi-step replays may overshoot by _SPG-1 steps
             tok_hist = torch.full((cache.max_seq + _SPG + 2,), -1,
                                   dtype=torch.int32, device=dev)
+            top_p_state = top_k_state = None
+            if filtered:
+                top_p_state = torch.tensor([float(top_p)], dtype=torch.float32,
+                                           device=dev)
+                top_k_state = torch.tensor([int(top_k)], dtype=torch.int32,
+                                           device=dev)
             W = self.model.new_decode_ws()
             W.logits.copy_(logits.reshape(1, -1))
             logits_buf = W.logits.view(-1)
@@ -375,8 +429,13 @@ class LocalEngine:
                 # ZERO allocations (capture-safe): sample from W.logits
                 # writes W.tok_long (the embedding index) in-kernel, the
                 # forward writes W.logits back.
-                hip.sample_state(logits_buf, temp_state, rng_state, tok_hist,
-                                 step_state, W.tok_long)
+                if filtered:
+                    hip.sample_state_filtered(
+                        logits_buf, temp_state, top_p_state, top_k_state,
+                        rng_state, tok_hist, step_state, W.tok_long)
+                else:
+                    hip.sample_state(logits_buf, temp_state, rng_state,
+                                     tok_hist, step_state, W.tok_long)
                 self.model.decode_step_ws(cache, pos_state, max_total, W)
                 hip.bump(pos_state, step_state)
 
@@ -432,7 +491,8 @@ class LocalEngine:
                         "key": key, "graph": graph, "pos_state": pos_state,
                         "step_state": step_state, "rng_state": rng_state,
                         "temp_state": temp_state, "tok_hist": tok_hist,
-                        "ws": W,
+                        "ws": W, "top_p_state": top_p_state,
+                        "top_k_state": top_k_state,
                     }
 
         CHECK = 32
@@ -494,7 +554,7 @@ def get_engine(spec: dict[str, Any], device: Optional[str] = None) -> LocalEngin
     """Process-wide engine cache: weights stay HBM-resident across rounds."""
     key = (spec.get("name"), spec.get("arch"), spec.get("weights"),
            spec.get("dtype"), resolve_kv_dtype(spec),
-           device or spec.get("gpu"))
+           device or spec.get("gpu"), resolve_sampling_filter(spec))
     with _ENGINES_LOCK:
         eng = _ENGINES.get(key)
         if eng is None:

@@ -17,6 +17,7 @@ from typing import Optional, Tuple
 
 import torch
 
+from ..providers import validate_sampling_filter
 from . import torch_ref
 
 _hip = None
@@ -596,3 +597,35 @@ def sample(
             seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
         return int(_require_hip().sample(logits, temperature, top_p, seed))
     return torch_ref.sample(logits, temperature, top_p, generator)
+
+
+def sample_filtered(
+    logits: torch.Tensor,
+    temperature: float = 0.7,
+    top_p: float = 1.0,
+    top_k: int = 0,
+    generator: Optional[torch.Generator] = None,
+    seed: Optional[int] = None,
+) -> int:
+    """Top-p / top-k filtered draw from a [vocab] logits row (the kept set
+    is torch_ref.nucleus_keep's). On GPU one kernel finds the cut and draws,
+    seeded by `seed`; on CPU the float64 reference draws with `generator`."""
+    top_p, top_k = validate_sampling_filter(top_p, top_k)
+    if _on_gpu(logits):
+        if seed is None:
+            seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+        return int(_require_hip().sample_filtered(
+            logits, temperature, top_p, top_k, seed))
+    return torch_ref.sample_filtered(logits, temperature, top_p, top_k,
+                                     generator)
+
+
+def nucleus_mask(logits: torch.Tensor, temperature: float, top_p: float,
+                 top_k: int = 0) -> torch.Tensor:
+    """The kept set of sample_filtered as bool [vocab]; on GPU it comes from
+    the sampling kernels' own cut."""
+    top_p, top_k = validate_sampling_filter(top_p, top_k)
+    if _on_gpu(logits):
+        return _require_hip().nucleus_mask(
+            logits, temperature, top_p, top_k).bool()
+    return torch_ref.nucleus_keep(logits, temperature, top_p, top_k)

@@ -977,6 +977,93 @@ void sample_state(torch::Tensor logits, torch::Tensor temp_state,
       cur_stream());
 }
 
+// ---- top-p / top-k filtered sampling --------------------------------------
+// Host-side argument checks shared by the three entries; the kernels index
+// the row as bf16x8 vectors and count tokens in float-exact integers.
+static int check_filtered_row(const char* who, const torch::Tensor& logits) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == at::kBFloat16,
+              who, ": logits must be a bf16 device tensor");
+  const int64_t vocab = logits.numel();
+  TORCH_CHECK(vocab > 0 && vocab % 8 == 0 && vocab < (1 << 24), who,
+              ": vocab must be a positive multiple of 8 below 2^24, got ",
+              vocab);
+  return (int)vocab;
+}
+
+static void check_filter_args(const char* who, double top_p, int64_t top_k) {
+  TORCH_CHECK(top_p > 0.0 && top_p <= 1.0, who, ": top_p must be in (0, 1], got ",
+              top_p);
+  TORCH_CHECK(top_k >= 0 && top_k <= INT32_MAX, who,
+              ": top_k must be >= 0, got ", top_k);
+}
+
+int64_t sample_filtered(torch::Tensor logits, double temp, double top_p,
+                        int64_t top_k, int64_t seed) {
+  const int vocab = check_filtered_row("sample_filtered", logits);
+  check_filter_args("sample_filtered", top_p, top_k);
+  auto lc = logits.contiguous();
+  auto out = torch::empty({1}, torch::TensorOptions()
+                                   .dtype(at::kInt)
+                                   .device(logits.device()));
+  launch_sample_filtered(uptr(lc), vocab, (float)temp, (float)top_p,
+                         (int)top_k, (uint32_t)seed, out.data_ptr<int>(),
+                         cur_stream());
+  return out.cpu().item<int>();
+}
+
+void sample_state_filtered(torch::Tensor logits, torch::Tensor temp_state,
+                           torch::Tensor top_p_state, torch::Tensor top_k_state,
+                           torch::Tensor rng_state, torch::Tensor tok_hist,
+                           torch::Tensor step_state, torch::Tensor tok_long) {
+  const int vocab = check_filtered_row("sample_state_filtered", logits);
+  TORCH_CHECK(logits.is_contiguous(),
+              "sample_state_filtered: logits must be contiguous (no copy is "
+              "made inside a captured step)");
+  TORCH_CHECK(temp_state.scalar_type() == at::kFloat && temp_state.is_cuda() &&
+                  temp_state.numel() >= 1,
+              "sample_state_filtered: temp_state must be a device f32 word");
+  TORCH_CHECK(top_p_state.scalar_type() == at::kFloat && top_p_state.is_cuda() &&
+                  top_p_state.numel() >= 1,
+              "sample_state_filtered: top_p_state must be a device f32 word");
+  TORCH_CHECK(top_k_state.scalar_type() == at::kInt && top_k_state.is_cuda() &&
+                  top_k_state.numel() >= 1,
+              "sample_state_filtered: top_k_state must be a device int32 word");
+  TORCH_CHECK(rng_state.scalar_type() == at::kInt && rng_state.is_cuda() &&
+                  rng_state.numel() >= 1,
+              "sample_state_filtered: rng_state must be a device int32 word");
+  TORCH_CHECK(step_state.scalar_type() == at::kInt && step_state.is_cuda() &&
+                  step_state.numel() >= 1,
+              "sample_state_filtered: step_state must be a device int32 word");
+  TORCH_CHECK(tok_hist.scalar_type() == at::kInt && tok_hist.is_cuda() &&
+                  tok_hist.is_contiguous() && tok_hist.numel() >= 1,
+              "sample_state_filtered: tok_hist must be device int32");
+  TORCH_CHECK(tok_long.scalar_type() == at::kLong && tok_long.is_cuda() &&
+                  tok_long.numel() >= 1,
+              "sample_state_filtered: tok_long must be int64 (the embedding "
+              "index)");
+  launch_sample_state_filtered(
+      uptr(logits), vocab, temp_state.data_ptr<float>(),
+      top_p_state.data_ptr<float>(), top_k_state.data_ptr<int>(),
+      reinterpret_cast<uint32_t*>(rng_state.data_ptr<int>()),
+      tok_hist.data_ptr<int>(), step_state.data_ptr<int>(),
+      reinterpret_cast<long long*>(tok_long.data_ptr<int64_t>()),
+      cur_stream());
+}
+
+// The kept set of a row as uint8 [vocab] (1 = kept), by the samplers' cut.
+torch::Tensor nucleus_mask(torch::Tensor logits, double temp, double top_p,
+                           int64_t top_k) {
+  const int vocab = check_filtered_row("nucleus_mask", logits);
+  check_filter_args("nucleus_mask", top_p, top_k);
+  auto lc = logits.contiguous();
+  auto mask = torch::empty({vocab}, torch::TensorOptions()
+                                        .dtype(at::kByte)
+                                        .device(logits.device()));
+  launch_nucleus_mask(uptr(lc), vocab, (float)temp, (float)top_p, (int)top_k,
+                      mask.data_ptr<uint8_t>(), cur_stream());
+  return mask;
+}
+
 // Release the decode-attention scratch entries whose keys (per-layer KV
 // cache base pointers) lie inside a dropped cache allocation, and free the
 // retired grown tensors. Call ONLY after every captured graph referencing
@@ -1123,6 +1210,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("kh"), py::arg("pos_state") = py::none());
   m.def("sample_state", &sample_state, "graph-mode on-device sampling");
   m.def("bump", &bump, "graph-mode pos/step bump");
+  m.def("sample_filtered", &sample_filtered,
+        "top-p / top-k filtered on-device sample",
+        py::arg("logits"), py::arg("temp"), py::arg("top_p"),
+        py::arg("top_k"), py::arg("seed"));
+  m.def("sample_state_filtered", &sample_state_filtered,
+        "graph-mode top-p / top-k filtered sampling",
+        py::arg("logits"), py::arg("temp_state"), py::arg("top_p_state"),
+        py::arg("top_k_state"), py::arg("rng_state"), py::arg("tok_hist"),
+        py::arg("step_state"), py::arg("tok_long"));
+  m.def("nucleus_mask", &nucleus_mask,
+        "kept set of a logits row under top-p / top-k, uint8 [vocab]",
+        py::arg("logits"), py::arg("temp"), py::arg("top_p"),
+        py::arg("top_k"));
   m.def("rope_kv_fp8", &rope_kv_fp8,
         "fused RoPE + rowwise-e4m3 quantizing paged KV append",
         py::arg("q"), py::arg("k"), py::arg("v"), py::arg("cost"),

@@ -88,6 +88,21 @@ void launch_sample_state(const ushort_t *logits, int vocab,
                          int *tok_hist, const int *step_state,
                          long long *tok_long, hipStream_t stream);
 void launch_bump(int *pos_state, int *step_state, hipStream_t stream);
+// top-p / top-k filtered twins (one 1024-thread block, ~128 KB static LDS);
+// top_p in (0, 1], top_k >= 0 (0 = off), vocab % 8 == 0, vocab < 2^24
+void launch_sample_filtered(const ushort_t *logits, int vocab, float temp,
+                            float top_p, int top_k, uint32_t seed, int *out,
+                            hipStream_t stream);
+void launch_sample_state_filtered(const ushort_t *logits, int vocab,
+                                  const float *temp_state,
+                                  const float *top_p_state,
+                                  const int *top_k_state, uint32_t *rng_state,
+                                  int *tok_hist, const int *step_state,
+                                  long long *tok_long, hipStream_t stream);
+// mask [vocab] uint8, 1 = kept, from the samplers' own cut
+void launch_nucleus_mask(const ushort_t *logits, int vocab, float temp,
+                         float top_p, int top_k, uint8_t *mask,
+                         hipStream_t stream);
 
 // ---- attention.hip --------------------------------------------------------
 // q [hq, hd]; kc, vc [n_pages, page, kh, hd]; out [hq, hd]. Runs the combine

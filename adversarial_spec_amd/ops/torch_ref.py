@@ -293,3 +293,64 @@ def sample(
         return int(idx[choice].item())
     choice = torch.multinomial(probs, 1, generator=generator)
     return int(choice.item())
+
+
+def nucleus_mass_above(
+    logits: torch.Tensor, temperature: float
+) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Per token of a [vocab] row, in float64: G, the softmax(logits / T)
+    probability of the tokens whose logit is strictly greater, and C, their
+    number (int64). Equal logits form one group and share (G, C); +0.0 and
+    -0.0 are equal (the row is taken `+ 0.0`, which turns -0.0 into +0.0
+    before grouping)."""
+    lf = logits.detach().reshape(-1).to(torch.float64) + 0.0
+    vals, inv, counts = torch.unique(
+        lf, sorted=True, return_inverse=True, return_counts=True)
+    w = torch.exp((vals - vals.max()) / temperature) * counts
+    gm = (w / w.sum()).flip(0)        # group masses, descending logit
+    gc = counts.flip(0)
+    zero = gm.new_zeros(1)
+    g_above = torch.cat([zero, gm.cumsum(0)[:-1]]).flip(0)
+    c_above = torch.cat([gc.new_zeros(1), gc.cumsum(0)[:-1]]).flip(0)
+    return g_above[inv], c_above[inv]
+
+
+def nucleus_keep(
+    logits: torch.Tensor, temperature: float, top_p: float, top_k: int = 0
+) -> torch.Tensor:
+    """The kept set of top-p / top-k filtering as bool [vocab]: token i is
+    kept iff G(i) < top_p and (top_k == 0 or C(i) < top_k), with G and C as
+    in nucleus_mass_above. A group of equal logits is kept or dropped whole
+    (the one difference from `sample`'s sorted-prefix rule, whose order
+    among equal elements is arbitrary), the argmax group is always kept,
+    and temperature <= 0 keeps the argmax group alone."""
+    if temperature <= 0.0:
+        lf = logits.detach().reshape(-1).to(torch.float64)
+        return lf == lf.max()
+    g_above, c_above = nucleus_mass_above(logits, temperature)
+    # in real arithmetic G < 1 for every token; in float64 a tail of zero
+    # weight rounds G up to 1.0, so top_p >= 1 is decided here, not compared
+    keep = g_above < top_p if top_p < 1.0 else torch.ones_like(g_above,
+                                                               dtype=torch.bool)
+    if top_k > 0:
+        keep &= c_above < top_k
+    return keep
+
+
+def sample_filtered(
+    logits: torch.Tensor,
+    temperature: float,
+    top_p: float,
+    top_k: int = 0,
+    generator: Optional[torch.Generator] = None,
+) -> int:
+    """A draw from softmax(logits / T) restricted to nucleus_keep and
+    renormalised; temperature <= 0 is the argmax (lowest index on ties)."""
+    lf = logits.detach().reshape(-1).to(torch.float64)
+    if temperature <= 0.0:
+        return int((lf == lf.max()).nonzero()[0].item())
+    keep = nucleus_keep(logits, temperature, top_p, top_k)
+    probs = torch.softmax(lf / temperature, dim=-1) * keep
+    probs = probs / probs.sum()
+    choice = torch.multinomial(probs, 1, generator=generator)
+    return int(choice.item())

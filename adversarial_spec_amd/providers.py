@@ -507,11 +507,29 @@ def handle_bedrock_command(subcommand: Optional[str], arg: Optional[str],
     return 1
 
 
+def validate_sampling_filter(top_p: Any, top_k: Any) -> tuple[float, int]:
+    """Range check of the truncated-sampling knobs, shared by the CLI, the
+    engine and the ops layer: 0 < top_p <= 1 (1 = off) and an integer
+    top_k >= 0 (0 = off). Returns them as (float, int); anything else is a
+    ValueError."""
+    if isinstance(top_p, bool) or not isinstance(top_p, (int, float)):
+        raise ValueError(f"top_p must be a number in (0, 1], got {top_p!r}")
+    if not 0.0 < float(top_p) <= 1.0:  # also rejects NaN
+        raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+    if isinstance(top_k, bool) or not isinstance(top_k, int):
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    if not 0 <= top_k < 2**31:
+        raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+    return float(top_p), int(top_k)
+
+
 def handle_local_command(subcommand: Optional[str], arg: Optional[str],
                          extra: Optional[str], weights: Optional[str],
                          gpu: Optional[int],
                          dtype: Optional[str] = None,
-                         kv_dtype: Optional[str] = None) -> int:
+                         kv_dtype: Optional[str] = None,
+                         top_p: Optional[float] = None,
+                         top_k: Optional[int] = None) -> int:
     """`debate.py local {status,add-model,remove-model,alias,list-models}` —
     manages the MI355X model registry section of the global config."""
     config = load_global_config()
@@ -555,8 +573,8 @@ def handle_local_command(subcommand: Optional[str], arg: Optional[str],
         return 1
     if subcommand == "alias":
         if not arg or not extra:
-            print("Error: usage: local alias <name> <arch> [--weights PATH] [--gpu N]",
-                  file=sys.stderr)
+            print("Error: usage: local alias <name> <arch> [--weights PATH] [--gpu N] "
+                  "[--top-p F] [--top-k N]", file=sys.stderr)
             return 1
         if extra not in LOCAL_MODEL_MAP and extra not in LOCAL_MODEL_MAP.values():
             print(f"Error: unknown arch '{extra}'", file=sys.stderr)
@@ -570,6 +588,19 @@ def handle_local_command(subcommand: Optional[str], arg: Optional[str],
             spec["dtype"] = dtype
         if kv_dtype:
             spec["kv_dtype"] = kv_dtype
+        if top_p is not None or top_k is not None:
+            # sampling defaults of the alias; only the given ones are stored
+            try:
+                p, k = validate_sampling_filter(
+                    1.0 if top_p is None else top_p,
+                    0 if top_k is None else top_k)
+            except ValueError as e:
+                print(f"Error: {e}", file=sys.stderr)
+                return 1
+            if top_p is not None:
+                spec["top_p"] = p
+            if top_k is not None:
+                spec["top_k"] = k
         local.setdefault("custom_aliases", {})[arg] = spec
         save_global_config(config)
         print(f"Local alias added: {arg} -> {json.dumps(spec)}")
