@@ -18,10 +18,8 @@
 //   page_table int32
 // State is fp32 throughout; hd in {32, 64, 128}; group = hq/kh <= 8.
 
-#include "common.h"
+#include "attn_decode_split.h"
 #include "launchers.h"
-
-#define MAXG 8
 
 // 16-lane-group dot reduce (LPP = lanes per position = hd/8)
 template <int LPP>
@@ -32,33 +30,85 @@ DEVINL float group_reduce_sum(float v) {
 }
 
 // ---------------------------------------------------------------------------
-// Decode split kernel.
-// grid.x = kh, grid.y = n_splits, block = 256 (4 waves).
-//
-// The KV read is staged through LDS by async global_load_lds in 64-position
-// double-buffered tiles (LDS-DMA keeps a whole tile in flight behind a
-// counted vmcnt — register-ring prefetch measured latency-bound).
-//
-// Compute is GROUP-PER-WAVE, LANE-PER-POSITION: wave w owns GQA head
-// group w (and w+4 at group 8); in the QK pass lane p holds position
-// tbase+p's full dot (the K image is chunk-XOR-swizzled so 16-lane b128
-// groups reading the same chunk index of 16 different rows stay
-// conflict-free), so the online-softmax reduce is ONE 6-level wave
-// reduction per 64-position tile — the old dim-sliced layout paid 4
-// shfl-chain levels per position per group (64+ chained DS ops per
-// tile). P values reach the dim-sliced PV pass by shfl broadcast: no
-// ds_write anywhere in the kernel (an LDS store makes hipcc order every
-// stage-image ds_read behind vmcnt(0), draining the DMA pipeline —
-// .s-verified round-2 failure mode).
-//
-// Workspace (fp32): ws_m, ws_l: [kh, n_splits, group]
-//                   ws_acc:     [kh, n_splits, group, hd]
+// Decode split kernel, bf16 cache: attn_decode_split_tiles
+// (attn_decode_split.h) over this trait. A 16-byte lane chunk is 8 elements
+// and a stage buffer is [K | V].
 // ---------------------------------------------------------------------------
 
-#define DTILE 64   // positions staged per LDS tile
+template <int HD_>
+struct KvBf16 {
+  static constexpr int HD = HD_, EPL = 8, LPP = HD / EPL;
+  static constexpr int TILE_E = DTILE * HD;  // elements per tensor per tile
+  static constexpr int BUF_B = 2 * TILE_E * 2;
+  static constexpr int LOADS_PER_TILE = LPP / 2;  // LPP/4 K + LPP/4 V pieces
+  static constexpr bool SCALED = false;
+  const ushort_t *kc, *vc;
 
+  // Each wave issues LPP/4 x 1 KiB pieces for K and for V; a piece covers
+  // WAVE/LPP consecutive positions; lane l handles the piece's position
+  // l/LPP, chunk l%LPP. The K source chunk is pre-swizzled, V stays linear.
+  template <bool IDENT>
+  DEVINL void stage_tile(uint8_t *buf, int t0, const SplitWave &w) const {
+    ushort_t *kimg = (ushort_t *)buf;
+    ushort_t *vimg = kimg + TILE_E;
+    const int sub = w.lane / LPP, sl = w.lane % LPP;
+#pragma unroll
+    for (int i = 0; i < LPP / 4; ++i) {  // pieces per wave per tensor
+      const int prow = (w.wid * (LPP / 4) + i) * (WAVE / LPP);  // tile-local
+      const int myrow = prow + sub;
+      const int pp = min(t0 + myrow, w.seq_len - 1);
+      const int phys = phys_page<IDENT>(w, pp);
+      const size_t row = ((size_t)phys * w.page + (pp % w.page)) * w.kh * HD +
+                         (size_t)w.g * HD;
+      glds16(kc + row + (size_t)(sl ^ kswz<LPP>(myrow)) * 8,
+             kimg + (size_t)prow * HD);
+      glds16(vc + row + sl * 8, vimg + (size_t)prow * HD);
+    }
+  }
+
+  // Heads outside, chunks inside (the K chunk is re-read per head): all of
+  // the work is in qk_head. 4 chunk-residue accumulators cover the
+  // dependent v_dot2 latency.
+  struct NoPart {};
+  template <int NG>
+  static DEVINL NoPart qk_chunks(const uint8_t *, const ushort_t *,
+                                 const SplitWave &, int) { return {}; }
+
+  static DEVINL float qk_head(NoPart, int gi, const uint8_t *buf,
+                              const ushort_t *qlds, const SplitWave &w) {
+    const int gq = w.wid + 4 * gi;
+    const ushort_t *kimg = (const ushort_t *)buf;
+    const int myswz = kswz<LPP>(w.lane);
+    float a4[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int c = 0; c < LPP; ++c) {
+      const v8s kv = ((const v8s *)(kimg + (size_t)w.lane * HD))[c];
+      const v8s qv = ((const v8s *)(qlds + (size_t)gq * HD))[c ^ myswz];
+      a4[c & 3] = dot8_bf16(__builtin_bit_cast(bf16x8, qv),
+                            __builtin_bit_cast(bf16x8, kv), a4[c & 3]);
+    }
+    return (a4[0] + a4[1]) + (a4[2] + a4[3]);
+  }
+
+  static DEVINL f32x8 load_v(const uint8_t *buf, int p, int sl) {
+    const ushort_t *vimg = (const ushort_t *)buf + TILE_E;
+    const v8s vv = ((const v8s *)(vimg + (size_t)p * HD))[sl];
+    return unpack8(__builtin_bit_cast(bf16x8, vv));
+  }
+};
+
+// `hd` stays in the argument list; the skeleton uses LPP * 8, which is the
+// only value the launcher passes.
+// The hd=32 one-head-per-wave instantiations need 62 VGPRs, two under the
+// 8-waves-per-SIMD step, and hipcc's scheduler gives that step up (74 VGPRs,
+// 6 waves) over source changes as small as moving the QK loop into a
+// function. The second launch bound states the occupancy they run at. It
+// also caps them at 64 VGPRs: an edit that needs more spills instead of
+// dropping an occupancy step, so check `.private_segment_fixed_size` of
+// these four symbols stays 0 whenever the skeleton changes.
 template <int LPP, int MG, bool IDENT>
-__global__ void __launch_bounds__(256) attn_decode_split_kernel(
+__global__ void __launch_bounds__(256, (LPP == 4 && MG <= 4) ? 8 : 1)
+attn_decode_split_kernel(
     const ushort_t *__restrict__ q,   // [hq, hd]
     const ushort_t *__restrict__ kc, const ushort_t *__restrict__ vc,
     const int *__restrict__ page_table, int seq_len, float scale,
@@ -66,232 +116,11 @@ __global__ void __launch_bounds__(256) attn_decode_split_kernel(
     float *__restrict__ ws_m, float *__restrict__ ws_l,
     float *__restrict__ ws_acc, const int *__restrict__ pos_ptr,
     ushort_t *__restrict__ out) {
-  // graph mode: seq_len = *pos_ptr + 1 (attend up to and incl. the token
-  // kv_write just appended at position *pos_ptr)
-  if (pos_ptr) seq_len = *pos_ptr + 1;
-  const int g = blockIdx.x;          // kv head
-  const int split = blockIdx.y;
-  const int n_splits = gridDim.y;
-  const int lane = threadIdx.x & (WAVE - 1);
-  const int wid = threadIdx.x / WAVE;
-  const int sub = lane / LPP;        // PV pass: position sub-group
-  const int sl = lane % LPP;         // PV pass: dim slice within position
-  const int subs = WAVE / LPP;       // concurrent positions per PV step
-  constexpr int NG = (MG + 3) / 4;   // GQA heads owned per wave
-
-  const int start = split * split_len;
-  const int limit = min(seq_len, (split + 1) * split_len);
-
-  // ONE shared array (guide §5 trap 4a): [2 stage buffers][K | V] + the
-  // q image. K images are chunk-swizzled; V and q are linear.
-  constexpr int TILE_E = DTILE * (LPP * 8);          // elements per tile
-  // The q image is written by whole-wave 16-B glds pieces (64 lanes x 8
-  // elements = 512 elements each, see below), so it is sized in whole
-  // pieces: MG*hd alone is under one piece for most instantiations and
-  // the DMA would land past the end of the array.
-  constexpr int QPIECE_E = WAVE * 8;
-  constexpr int QPIECES = (MG * LPP * 8 + QPIECE_E - 1) / QPIECE_E;
-  constexpr int QIMG_E = QPIECES * QPIECE_E;
-  __shared__ __attribute__((aligned(16))) ushort_t lds[4 * TILE_E + QIMG_E];
-  ushort_t *qlds = lds + 4 * TILE_E;
-
-  // K chunk swizzle: a 256-B LDS bank row holds 32/LPP image rows, so
-  // same-chunk reads of two rows collide whenever the rows share a
-  // bank-row offset (p ≡ p' mod 16/LPP); XOR the chunk index with the
-  // row's bank-alias class to spread them.
-  constexpr int SWZ_DIV = 16 / LPP;  // rows sharing a bank-row offset
-  auto kswz = [&](int row) { return (row / SWZ_DIV) & (LPP - 1); };
-
-  float m[NG], l[NG], acc[NG][8];
-#pragma unroll
-  for (int gi = 0; gi < NG; ++gi) {
-    m[gi] = -INFINITY;
-    l[gi] = 0.f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[gi][j] = 0.f;
-  }
-
-  // stage one DTILE-position K/V tile into LDS buffer b via glds.
-  // Each wave issues LPP/4 x 1 KiB pieces for K and for V; a piece covers
-  // `subs` consecutive positions; lane l handles the piece's position
-  // l/LPP, chunk l%LPP — lane-linear in LDS as glds requires. The K
-  // SOURCE chunk is pre-swizzled (kswz involution) so the lane-linear
-  // LDS image realizes the swizzled layout; V stays linear. Out-of-range
-  // positions clamp to a valid row (their scores are masked in compute).
-  auto stage_tile = [&](int t0, int b) {
-    ushort_t *kimg = lds + (size_t)b * 2 * TILE_E;
-    ushort_t *vimg = kimg + TILE_E;
-#pragma unroll
-    for (int i = 0; i < LPP / 4; ++i) {  // pieces per wave per tensor
-      const int prow = (wid * (LPP / 4) + i) * subs;  // tile-local row
-      const int myrow = prow + sub;
-      const int pp = min(t0 + myrow, seq_len - 1);
-      // IDENT: the engine's single-pool cache uses the identity page
-      // table — pure address math, no table read. The general path pays
-      // an ordinary VMEM load here (hipcc then drains the DMA queue at
-      // its use — correct but slower; only non-identity tables take it).
-      const int phys = IDENT ? (pp / page) : page_table[pp / page];
-      const size_t row = ((size_t)phys * page + (pp % page)) * kh * hd +
-                         (size_t)g * hd;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void
-               *)(kc + row + (size_t)(sl ^ kswz(myrow)) * 8),
-          (__attribute__((address_space(3))) void *)(kimg +
-                                                     (size_t)prow * hd),
-          16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void *)(vc + row + sl * 8),
-          (__attribute__((address_space(3))) void *)(vimg +
-                                                     (size_t)prow * hd),
-          16, 0, 0);
-    }
-  };
-
-  // stage q (group*hd elements) by glds from wave 0 — staged, not plain
-  // loads: an ordinary VMEM load whose wait lands inside the tile loop
-  // forces hipcc to a loop-variant count, i.e. `vmcnt(0)` per iteration,
-  // draining the DMA pipeline (.s-verified failure mode). The q pieces
-  // are issued BEFORE the K/V prologue, so wave 0's first counted wait
-  // covers them and the barrier publishes the image.
-  typedef __attribute__((__vector_size__(8 * sizeof(short)))) short v8s;
-  if (wid == 0) {
-#pragma unroll
-    for (int i = 0; i < QPIECES; ++i) {
-      if (i * QPIECE_E >= group * hd) break;  // uniform: MG may exceed group
-      const int off8 = min(i * QPIECE_E + lane * 8, group * hd - 8);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void
-               *)(q + (size_t)(g * group) * hd + off8),
-          (__attribute__((address_space(3))) void *)(qlds + i * QPIECE_E), 16,
-          0, 0);
-    }
-  }
-
-  const int ntiles = (limit - start + DTILE - 1) / DTILE;
-  float pex[NG];
-  if (ntiles > 0) {
-    stage_tile(start, 0);
-    if (ntiles > 1) stage_tile(start + DTILE, 1);
-
-    for (int t = 0; t < ntiles; ++t) {
-      // wait for tile t's DMA (tile t+1 stays in flight: 2 tensors x
-      // LPP/4 pieces per wave = LPP/2 loads outstanding), then align.
-      // Wave 0's q pieces are OLDER than tile 0's, so the same counted
-      // wait covers them.
-      if (ntiles > t + 1) {
-        if (LPP == 16) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (LPP == 8) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-      } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      }
-      __builtin_amdgcn_s_barrier();
-      const ushort_t *kimg = lds + (size_t)(t & 1) * 2 * TILE_E;
-      const ushort_t *vimg = kimg + TILE_E;
-      const int tbase = start + t * DTILE;
-
-      // ---- QK: lane-per-position full dot (4 chunk-residue
-      // accumulators cover the dependent v_dot2 latency) ----
-      const bool valid = tbase + lane < limit;
-      const int myswz = kswz(lane);
-#pragma unroll
-      for (int gi = 0; gi < NG; ++gi) {
-        const int gq = wid + 4 * gi;
-        if (gq >= group) break;  // wave-uniform
-        float a4[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int c = 0; c < LPP; ++c) {
-          const v8s kv = ((const v8s *)(kimg + (size_t)lane * hd))[c];
-          const v8s qv =
-              ((const v8s *)(qlds + (size_t)gq * hd))[c ^ myswz];
-          a4[c & 3] = dot8_bf16(__builtin_bit_cast(bf16x8, qv),
-                                __builtin_bit_cast(bf16x8, kv), a4[c & 3]);
-        }
-        const float s = (a4[0] + a4[1]) + (a4[2] + a4[3]);  // raw dot
-
-        // ---- online softmax for this wave's head in the LOG2-SCALED
-        // domain (m tracks m2 = max*scale*log2e; p = exp2(fma(s, scale2,
-        // -m2)) — one fma+exp per element, no scale/sub passes); ONE
-        // wave-wide max/sum pair per tile ----
-        const float scale2 = scale * 1.4426950408889634f;
-        float mx = valid ? s : -INFINITY;
-        mx = wave_reduce_max(mx);
-        const float mx2 = mx * scale2;
-        const float mn = fmaxf(m[gi], mx2);
-        const float alpha = (mn == -INFINITY) ? 0.f : exp2f(m[gi] - mn);
-        const float p =
-            (valid && mn != -INFINITY)
-                ? exp2f(__builtin_fmaf(s, scale2, -mn))
-                : 0.f;
-        const float ps = wave_reduce_sum(p);
-        l[gi] = l[gi] * alpha + ps;
-        m[gi] = mn;
-        pex[gi] = p;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) acc[gi][j] *= alpha;
-      }
-
-      // ---- PV: dim-sliced; this tile's P values arrive by shfl from
-      // the lane that owns the position (no LDS write — see header) ----
-#pragma unroll 4
-      for (int it = 0; it < LPP; ++it) {
-        const int p = it * subs + sub;
-        const v8s vv = ((const v8s *)(vimg + (size_t)p * hd))[sl];
-        const f32x8 vd = unpack8(__builtin_bit_cast(bf16x8, vv));
-#pragma unroll
-        for (int gi = 0; gi < NG; ++gi) {
-          if (wid + 4 * gi >= group) break;
-          const float pw = __shfl(pex[gi], p, WAVE);
-#pragma unroll
-          for (int j = 0; j < 8; ++j)
-            acc[gi][j] = fmaf(pw, vd.v[j], acc[gi][j]);
-        }
-      }
-
-      // issue tile t+2 into the buffer just consumed — after re-aligning
-      // so no wave still reads it
-      __builtin_amdgcn_s_barrier();
-      if (t + 2 < ntiles) stage_tile(tbase + 2 * DTILE, t & 1);
-    }
-  }
-
-  // ---- merge the PV sub-partitions (lanes xor LPP, 2*LPP, ...) and
-  // write this split's state. m/l are already wave-uniform; each wave
-  // owns its head(s), so there is NO cross-wave merge at all. ----
-#pragma unroll
-  for (int off = LPP; off < WAVE; off <<= 1)
-#pragma unroll
-    for (int gi = 0; gi < NG; ++gi)
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[gi][j] += __shfl_xor(acc[gi][j], off, WAVE);
-
-#pragma unroll
-  for (int gi = 0; gi < NG; ++gi) {
-    const int gq = wid + 4 * gi;
-    if (gq >= group) break;
-    if (n_splits == 1) {
-      // whole softmax state in this block: write the output directly
-      if (lane < LPP) {
-        const float inv = (l[gi] > 0.f) ? 1.0f / l[gi] : 0.f;
-        bf16x8 o;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) o.u[j] = f32_to_bf16(acc[gi][j] * inv);
-        ((bf16x8 *)(out + (size_t)(g * group + gq) * hd))[sl] = o;
-      }
-    } else {
-      const size_t base = ((size_t)g * n_splits + split) * group + gq;
-      if (lane == 0) {
-        ws_m[base] = m[gi];
-        ws_l[base] = l[gi];
-      }
-      if (lane < LPP) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j)
-          ws_acc[base * hd + sl * 8 + j] = acc[gi][j];
-      }
-    }
-  }
+  attn_decode_split_tiles<KvBf16<LPP * 8>, MG, IDENT>(
+      {kc, vc}, q, page_table, seq_len, scale, kh, group, page, split_len,
+      ws_m, ws_l, ws_acc, pos_ptr, out);
 }
+
 
 // ---------------------------------------------------------------------------
 // Decode combine kernel: grid = (hq, hd/64), block = 256 (4 waves).
@@ -528,36 +357,15 @@ extern "C" void launch_attn_decode_split(const ushort_t *q, const ushort_t *kc,
                                          const ushort_t *vc,
                                          const DecodeSplitArgs &a,
                                          ushort_t *out, hipStream_t stream) {
-  dim3 grid(a.kh, a.n_splits);
-  const int lds = 0;  // all LDS is static in the kernel (stage + merge)
-  // MG = smallest supported bound >= group keeps the per-head state arrays
-  // (q fragments + online-softmax accumulators) sized to the real GQA
-  // group; IDENT elides the page-table read (identity single-pool cache).
-#define DISPATCH_ONE(LPP, MG)                                                  \
-  do {                                                                         \
-    if (a.identity)                                                            \
-      attn_decode_split_kernel<LPP, MG, true><<<grid, 256, lds, stream>>>(     \
-          q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,    \
-          a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);      \
-    else                                                                       \
-      attn_decode_split_kernel<LPP, MG, false><<<grid, 256, lds, stream>>>(    \
-          q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,    \
-          a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);      \
-  } while (0)
-#define DISPATCH_MG(LPP)                                                       \
-  do {                                                                         \
-    if (a.group <= 2) DISPATCH_ONE(LPP, 2);                                    \
-    else if (a.group <= 4) DISPATCH_ONE(LPP, 4);                               \
-    else DISPATCH_ONE(LPP, 8);                                                 \
-  } while (0)
-
-  switch (a.hd / 8) {
-    case 4: DISPATCH_MG(4); break;
-    case 8: DISPATCH_MG(8); break;
-    case 16: DISPATCH_MG(16); break;
-  }
-#undef DISPATCH_MG
-#undef DISPATCH_ONE
+  const dim3 grid(a.kh, a.n_splits);
+  dispatch_decode_split(a.hd, a.group, a.identity, [&](auto HD, auto MG,
+                                                       auto IDENT) {
+    attn_decode_split_kernel<decltype(HD)::value / 8, decltype(MG)::value,
+                             decltype(IDENT)::value>
+        <<<grid, 256, 0, stream>>>(  // all LDS is static in the kernel
+            q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,
+            a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);
+  });
   if (a.n_splits > 1) {
     launch_attn_decode_combine(a.ws_m, a.ws_l, a.ws_acc, out, a.n_splits,
                                a.kh, a.group, a.hd, stream);

@@ -10,22 +10,18 @@
 //   bits rope_kv writes to a bf16 cache).
 //
 //  - rope_kv_fp8_kernel: fp8 twin of rope_kv_kernel (elementwise.hip).
-//  - attn_decode_split_fp8_kernel: fp8 twin of attn_decode_split_kernel
-//    (attention.hip) with the dequantization folded into the softmax; it
-//    writes the same workspace and is followed by the same
+//  - attn_decode_split_fp8_kernel: fp8 twin of the decode split kernel
+//    (attn_decode_split.h) with the dequantization folded into the softmax;
+//    it writes the same workspace and is followed by the same
 //    attn_decode_combine_kernel.
 //  - kv_dequant_fp8_kernel: gathers positions [0, n) into contiguous bf16
 //    (chunked prefill only).
 // hd in {32, 64, 128}; group = hq/kh <= 8.
 
-#include "common.h"
+#include "attn_decode_split.h"
 #include "launchers.h"
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-// 16-byte LDS reads go through a plain vector type: a ds_read of a struct
-// type (uint4) carries no alias info, and hipcc then orders it behind
-// vmcnt(0) while a global_load_lds is in flight (.s-verified).
-typedef uint32_t u32x4v __attribute__((ext_vector_type(4)));
 
 #define E4M3_MAX 448.0f
 
@@ -168,12 +164,13 @@ kv_dequant_fp8_kernel(const uint8_t *__restrict__ kc,
 // Decode split kernel, fp8 cache.
 // grid.x = kh, grid.y = n_splits, block = 256 (4 waves).
 //
-// Same structure as attn_decode_split_kernel: 64-position tiles staged into
-// LDS by async global_load_lds, double-buffered behind a counted vmcnt;
-// group-per-wave, lane-per-position QK against a chunk-XOR-swizzled K image;
-// one wave reduction pair per tile; P reaches the dim-sliced PV pass by shfl
-// broadcast; no ds_write anywhere (see attention.hip for the failure modes
-// behind each of these).
+// The tile loop of attn_decode_split_tiles (attn_decode_split.h), KEPT IN
+// THE SPELLING IT HAD BEFORE THAT SKELETON EXISTED: built from the skeleton
+// over an fp8 trait this kernel had the same instruction counts and, at
+// hd=128, an instruction-identical tile loop, and still measured 2 % slower
+// solo (17.07 vs 16.68 us at 8k) for a reason that was not found. Every
+// mechanism note in the skeleton's header holds here; a change to the ring,
+// the waits or the softmax is made there AND here.
 //
 // What the 1-byte rows change:
 //   - a 16-byte lane chunk is 16 elements, a row is C16 = hd/16 chunks and a
@@ -202,8 +199,6 @@ kv_dequant_fp8_kernel(const uint8_t *__restrict__ kc,
 // Positions >= seq_len clamp to the last valid row for the rows AND the
 // scales, so nothing past the sequence is ever read.
 // ---------------------------------------------------------------------------
-
-#define DTILE 64   // positions staged per LDS tile
 
 // 4 e4m3 bytes of `w` -> two packed bf16 pairs
 DEVINL void fp8x4_to_bf16x4(uint32_t w, uint32_t &p01, uint32_t &p23) {
@@ -497,34 +492,16 @@ extern "C" void launch_attn_decode_split_fp8(const ushort_t *q,
                                              const DecodeSplitArgs &a,
                                              ushort_t *out,
                                              hipStream_t stream) {
-  dim3 grid(a.kh, a.n_splits);
-#define DISPATCH_ONE(HD, MG)                                                   \
-  do {                                                                         \
-    if (a.identity)                                                            \
-      attn_decode_split_fp8_kernel<HD, MG, true><<<grid, 256, 0, stream>>>(    \
-          q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,         \
-          a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,   \
-          out);                                                                \
-    else                                                                       \
-      attn_decode_split_fp8_kernel<HD, MG, false><<<grid, 256, 0, stream>>>(   \
-          q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,         \
-          a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,   \
-          out);                                                                \
-  } while (0)
-#define DISPATCH_MG(HD)                                                        \
-  do {                                                                         \
-    if (a.group <= 2) DISPATCH_ONE(HD, 2);                                     \
-    else if (a.group <= 4) DISPATCH_ONE(HD, 4);                                \
-    else DISPATCH_ONE(HD, 8);                                                  \
-  } while (0)
-
-  switch (a.hd) {
-    case 32: DISPATCH_MG(32); break;
-    case 64: DISPATCH_MG(64); break;
-    case 128: DISPATCH_MG(128); break;
-  }
-#undef DISPATCH_MG
-#undef DISPATCH_ONE
+  const dim3 grid(a.kh, a.n_splits);
+  dispatch_decode_split(a.hd, a.group, a.identity, [&](auto HD, auto MG,
+                                                       auto IDENT) {
+    attn_decode_split_fp8_kernel<decltype(HD)::value, decltype(MG)::value,
+                                 decltype(IDENT)::value>
+        <<<grid, 256, 0, stream>>>(
+            q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,
+            a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,
+            out);
+  });
   if (a.n_splits > 1) {
     // the bf16 path's combine pass (attention.hip), shared unchanged
     launch_attn_decode_combine(a.ws_m, a.ws_l, a.ws_acc, out, a.n_splits,

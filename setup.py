@@ -40,6 +40,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "common.h"),
         os.path.join(HIP_DIR, "rope_epilogue.h"),
         os.path.join(HIP_DIR, "gemv_rows.h"),
+        os.path.join(HIP_DIR, "attn_decode_split.h"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
