@@ -688,14 +688,24 @@ void gemv_gateup_norm(torch::Tensor x, torch::Tensor wln, torch::Tensor w,
                           F2 / 2, (float)eps, cur_stream());
 }
 
+// Operands of the bf16 prefill GEMMs, checked before anything is allocated
+// or launched. The kernels stage A and B in 16-byte chunks of 8 elements, so
+// K % 8 == 0 keeps every row 16-byte aligned and leaves no sub-chunk tail.
+static void check_gemm_operands(const char* who, const torch::Tensor& a,
+                                const torch::Tensor& b) {
+  TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2,
+              who, ": a bf16 [M, K] on GPU");
+  TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kBFloat16 && b.dim() == 2,
+              who, ": b bf16 [N, K] (row-major weights) on GPU");
+  TORCH_CHECK(a.size(1) == b.size(1), who, ": K mismatch");
+  TORCH_CHECK(a.size(1) % 8 == 0, who, ": K % 8 == 0");
+}
+
 // Tiled MFMA GEMM: C = A @ B, bf16, fp32 accumulation. Replaces library
 // GEMMs on the prefill path (deterministic, workspace-free; see gemm.hip).
 torch::Tensor gemm(torch::Tensor a, torch::Tensor b) {
   // C = a @ b^T with b stored row-major [N, K] (HF layout)
-  CHECK_BF16_CUDA(a);
-  CHECK_BF16_CUDA(b);
-  TORCH_CHECK(a.dim() == 2 && b.dim() == 2, "gemm: 2-D inputs");
-  TORCH_CHECK(a.size(1) == b.size(1), "gemm: K mismatch");
+  check_gemm_operands("gemm", a, b);
   auto ac = a.contiguous();
   auto bc = b.contiguous();
   const int M = ac.size(0), K = ac.size(1), N = bc.size(0);
@@ -715,14 +725,16 @@ torch::Tensor gemm(torch::Tensor a, torch::Tensor b) {
 // deep-pipelined) — A/B microbenches and the race screen; production code
 // uses gemm()'s dispatcher.
 torch::Tensor gemm_variant(torch::Tensor a, torch::Tensor b, int64_t which) {
-  CHECK_BF16_CUDA(a);
-  CHECK_BF16_CUDA(b);
+  check_gemm_operands("gemm_variant", a, b);
+  TORCH_CHECK(which == 128 || which == 256,
+              "gemm_variant: which is 128 or 256");
+  TORCH_CHECK(which == 128 || (a.size(1) >= 512 && a.size(1) % 128 == 0),
+              "gemm256 needs K%128==0, K>=512");
   auto ac = a.contiguous();
   auto bc = b.contiguous();
   const int M = ac.size(0), K = ac.size(1), N = bc.size(0);
   auto c = torch::empty({M, N}, ac.options());
   if (which == 256) {
-    TORCH_CHECK(K >= 512 && K % 128 == 0, "gemm256 needs K%128==0, K>=512");
     launch_gemm256(uptr(ac), uptr(bc), uptr_mut(c), M, N, K, cur_stream());
   } else {
     launch_gemm(uptr(ac), uptr(bc), uptr_mut(c), M, N, K, cur_stream());
@@ -750,14 +762,30 @@ void quant_fp8(torch::Tensor x, torch::Tensor q, torch::Tensor scale) {
                    M, K, cur_stream());
 }
 
+// Operands shared by the fp8 GEMM and the fp8 decode GEMVs, checked before
+// any launch. The kernels stream w8 and x8 in 16-byte chunks of 16 codes
+// (nc = K / 16), so a K that is no multiple of 16 would silently drop the row
+// tails (and, in the GEMM, leave its 16-byte loads only 8-byte aligned).
+static void check_fp8_weight(const char* who, const torch::Tensor& w8,
+                             const torch::Tensor& wsc) {
+  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 2 &&
+                  w8.is_contiguous(),
+              who, ": w8 contiguous uint8 [N, K] (e4m3fn bytes) on GPU");
+  TORCH_CHECK(w8.size(1) % 16 == 0, who, ": K % 16 == 0");
+  TORCH_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat &&
+                  wsc.is_contiguous() && wsc.numel() >= w8.size(0),
+              who, ": wsc contiguous f32, one scale per weight row, on GPU");
+}
+
 // fp8 GEMM: C = (x quantized rowwise) @ (w8 * wsc)^T; w8 row-major [N,K]
 // e4m3 + per-row scale. x is quantized in here (eager prefill path).
 torch::Tensor gemm_fp8(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc) {
   CHECK_BF16_CUDA(x);
-  TORCH_CHECK(w8.scalar_type() == at::kByte && w8.is_contiguous());
+  TORCH_CHECK(x.dim() == 2, "gemm_fp8: x bf16 [M, K]");
+  check_fp8_weight("gemm_fp8", w8, wsc);
+  TORCH_CHECK(w8.size(1) == x.size(1), "gemm_fp8: K mismatch");
   auto xc = x.contiguous();
   const int M = xc.size(0), K = xc.size(1), N = w8.size(0);
-  TORCH_CHECK(w8.size(1) == K, "gemm_fp8: K mismatch");
   auto opts8 = torch::TensorOptions().dtype(at::kByte).device(x.device());
   auto optsf = torch::TensorOptions().dtype(at::kFloat).device(x.device());
   auto x8 = torch::empty({M, (long)K}, opts8);
@@ -777,20 +805,6 @@ torch::Tensor gemm_fp8(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc) {
                     uptr_mut(c), M, N, K, cur_stream());
   }
   return c;
-}
-
-// Operands shared by the fp8 decode GEMVs, checked before any launch. The
-// kernels stream w8 and x8 in 16-byte chunks of 16 codes (nc = K / 16), so a
-// K that is no multiple of 16 would silently drop the row tails.
-static void check_fp8_weight(const char* who, const torch::Tensor& w8,
-                             const torch::Tensor& wsc) {
-  TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 2 &&
-                  w8.is_contiguous(),
-              who, ": w8 contiguous uint8 [N, K] (e4m3fn bytes) on GPU");
-  TORCH_CHECK(w8.size(1) % 16 == 0, who, ": K % 16 == 0");
-  TORCH_CHECK(wsc.is_cuda() && wsc.scalar_type() == at::kFloat &&
-                  wsc.is_contiguous() && wsc.numel() >= w8.size(0),
-              who, ": wsc contiguous f32, one scale per weight row, on GPU");
 }
 
 // The quantized activation: x8 holds at least K codes (the decode workspace

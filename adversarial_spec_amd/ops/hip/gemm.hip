@@ -23,6 +23,11 @@
 //   - fragment reads de-swizzle with the same XOR.
 // Edge tiles (M/N/K not tile-aligned) take a guarded register-staging
 // path into the same swizzled image, so the MFMA loop is shared.
+//
+// K contract: the bindings (gemm, gemm_variant in bindings.hip) guarantee
+// K % 8 == 0, so every row starts 16-byte aligned and a K edge always ends
+// on a whole 16 B chunk. The sub-chunk arm of stage_edge (the element-wise
+// copy when gk + 8 > k_left) is therefore unreachable through them.
 
 #include "common.h"
 #include "launchers.h"

@@ -12,6 +12,11 @@
 // double-buffered global_load_lds staging, source-XOR swizzle) with
 // half-width rows: an image row is 64 B (4 x 16 B chunks), fragments are
 // 8 fp8 = 8 B per lane read as the low/high half of a swizzled 16 B chunk.
+//
+// K contract: the binding (gemm_fp8 in bindings.hip) guarantees
+// K % 16 == 0, so every row of A8 and B8 starts 16-byte aligned (the glds
+// staging loads 16 B per lane) and the rowwise quantizer, which walks K in
+// chunks of 8, writes every code the GEMM reads.
 
 #include "common.h"
 #include "launchers.h"
