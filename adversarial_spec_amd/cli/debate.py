@@ -66,6 +66,14 @@ def _top_k_arg(text: str) -> int:
         raise argparse.ArgumentTypeError(str(e)) from None
 
 
+def _sliding_window_arg(text: str) -> int:
+    """argparse type of --sliding-window: range-checked at parse time."""
+    try:
+        return providers.validate_sliding_window(int(text))
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+
+
 def create_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(
         prog="debate.py",
@@ -153,6 +161,12 @@ Bedrock:
                         help="KV-cache storage for `local alias` (fp8 = "
                              "rowwise e4m3 cache, half the KV bytes; "
                              "independent of --model-dtype)")
+    parser.add_argument("--sliding-window", type=_sliding_window_arg,
+                        default=None,
+                        help="Sliding attention window for `local alias`: "
+                             "each position attends its last N keys, itself "
+                             "included (0 = full causal attention; default: "
+                             "the checkpoint's config.json, then the preset)")
     parser.add_argument("--top-p", type=_top_p_arg, default=None,
                         help="Default nucleus (top-p) sampling cut-off for "
                              "`local alias`, 0 < p <= 1 (1 = off)")
@@ -253,7 +267,7 @@ def handle_utility_command(args: argparse.Namespace) -> Optional[int]:
         return providers.handle_local_command(
             args.profile_name, args.bedrock_arg, args.extra_arg,
             args.weights, args.gpu, args.model_dtype, args.kv_dtype,
-            args.top_p, args.top_k,
+            args.top_p, args.top_k, args.sliding_window,
         )
     return None
 

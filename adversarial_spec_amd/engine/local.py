@@ -12,6 +12,8 @@ in HBM3E between rounds, so round k+1 pays only prefill+decode.
 
 from __future__ import annotations
 
+import dataclasses
+import json
 import os
 import threading
 import time
@@ -22,7 +24,7 @@ import torch
 from .. import ops
 from ..models import LlamaModel, get_config
 from ..models.llama import KV_DTYPES
-from ..providers import validate_sampling_filter
+from ..providers import validate_sampling_filter, validate_sliding_window
 from ..utils.timing import PhaseTimer
 from .tokenizer import build_tokenizer
 
@@ -75,6 +77,30 @@ def resolve_kv_dtype(spec: dict[str, Any]) -> str:
     return kv
 
 
+def resolve_sliding_window(spec: dict[str, Any], config,
+                           weights_dir: Optional[str] = None) -> int:
+    """Sliding attention window of an engine, an int >= 0 (0 = full causal
+    attention): the spec key `sliding_window`; when the key is absent, the
+    `sliding_window` entry of `<weights_dir>/config.json` if that file
+    exists (a checkpoint that says `null` has no window: 0); otherwise the
+    preset's (`config.sliding_window`). Bools, non-integers and negatives
+    are a ValueError."""
+    value, source = spec.get("sliding_window"), "spec"
+    if value is None and weights_dir:
+        path = os.path.join(weights_dir, "config.json")
+        if os.path.isfile(path):
+            with open(path) as f:
+                ckpt = json.load(f)
+            if isinstance(ckpt, dict) and "sliding_window" in ckpt:
+                value = ckpt["sliding_window"]
+                source = path
+                if value is None:
+                    return 0
+    if value is None:
+        value, source = config.sliding_window, "preset"
+    return validate_sliding_window(value, source)
+
+
 def resolve_sampling_filter(spec: dict[str, Any]) -> tuple[float, int]:
     """An engine's default truncated-sampling setting: the optional spec keys
     `top_p` (0 < top_p <= 1) and `top_k` (integer >= 0), falling back to
@@ -99,6 +125,12 @@ class LocalEngine:
         self.name = spec.get("name", spec["arch"])
         self.arch = spec["arch"]
         self.config = get_config(self.arch)
+        # the window the checkpoint was trained with (or the spec asks for)
+        # replaces the preset's before the model is built
+        window = resolve_sliding_window(spec, self.config, spec.get("weights"))
+        if window != self.config.sliding_window:
+            self.config = dataclasses.replace(self.config,
+                                              sliding_window=window)
         if device is None:
             gpu = spec.get("gpu")
             if torch.cuda.is_available():
@@ -554,7 +586,8 @@ def get_engine(spec: dict[str, Any], device: Optional[str] = None) -> LocalEngin
     """Process-wide engine cache: weights stay HBM-resident across rounds."""
     key = (spec.get("name"), spec.get("arch"), spec.get("weights"),
            spec.get("dtype"), resolve_kv_dtype(spec),
-           device or spec.get("gpu"), resolve_sampling_filter(spec))
+           device or spec.get("gpu"), resolve_sampling_filter(spec),
+           spec.get("sliding_window"))
     with _ENGINES_LOCK:
         eng = _ENGINES.get(key)
         if eng is None:

@@ -26,6 +26,9 @@ class LlamaConfig:
     # explicit head_dim survives tensor-parallel sharding (where n_heads
     # shrinks but the per-head width does not); None derives dim/n_heads.
     head_dim_override: int = 0
+    # sliding attention window W: position i sees keys max(0, i-W+1)..i
+    # (W keys including itself, the HF Mistral convention); 0 = full causal.
+    sliding_window: int = 0
 
     @property
     def head_dim(self) -> int:
@@ -58,6 +61,13 @@ PRESETS: dict[str, LlamaConfig] = {
     "mistral-7b": LlamaConfig(
         name="mistral-7b", dim=4096, n_layers=32, n_heads=32, n_kv_heads=8,
         ffn_dim=14336, vocab_size=32000, max_seq_len=32768, rope_theta=10000.0,
+    ),
+    # Mistral-7B-v0.1 as trained: the same network behind a 4096-token
+    # sliding attention window.
+    "mistral-7b-v0.1": LlamaConfig(
+        name="mistral-7b-v0.1", dim=4096, n_layers=32, n_heads=32,
+        n_kv_heads=8, ffn_dim=14336, vocab_size=32000, max_seq_len=32768,
+        rope_theta=10000.0, sliding_window=4096,
     ),
     # CPU-testable / smoke model: byte tokenizer fits in 1024 vocab.
     "tiny": LlamaConfig(

@@ -438,7 +438,8 @@ class LlamaModel:
                 if pos0 == 0:
                     # (fp8 cache too: single-shot prefill attends over the
                     # fresh unquantized K/V; only the cache copy is fp8)
-                    attn = ops.attn_prefill(q, k, v, self.scale, causal=True)
+                    attn = ops.attn_prefill(q, k, v, self.scale, causal=True,
+                                            window=c.sliding_window)
                 elif kv8:
                     # chunked prefill over an fp8 cache: the prefix (this
                     # chunk's own rows included) is read back dequantized,
@@ -449,7 +450,8 @@ class LlamaModel:
                         cache.v_scale[i], cache.page_table, pos0 + t,
                         dtype=q.dtype)
                     attn = ops.attn_prefill(q, k_all, v_all, self.scale,
-                                            causal=True, kv_offset=pos0)
+                                            causal=True, kv_offset=pos0,
+                                            window=c.sliding_window)
                 else:
                     # chunked prefill: this chunk's queries attend to ALL
                     # cached positions plus themselves. The page table is
@@ -460,7 +462,8 @@ class LlamaModel:
                     k_all = cache.k[i].view(-1, kh_, hd)[: pos0 + t]
                     v_all = cache.v[i].view(-1, kh_, hd)[: pos0 + t]
                     attn = ops.attn_prefill(q, k_all, v_all, self.scale,
-                                            causal=True, kv_offset=pos0)
+                                            causal=True, kv_offset=pos0,
+                                            window=c.sliding_window)
             else:
                 seq = max_seq_bound if pos_state is not None else pos0 + 1
                 if kv8:
@@ -469,6 +472,7 @@ class LlamaModel:
                         cache.v_scale[i], cache.page_table, seq, self.scale,
                         pos_state=pos_state, identity=cache.identity,
                         split_blocks=self.split_blocks,
+                        window=c.sliding_window,
                     ).unsqueeze(0)
                 else:
                     attn = ops.attn_decode_paged(
@@ -476,6 +480,7 @@ class LlamaModel:
                         self.scale, pos_state=pos_state,
                         identity=cache.identity,
                         split_blocks=self.split_blocks,
+                        window=c.sliding_window,
                     ).unsqueeze(0)
             attn_out = proj(attn.reshape(t, h * hd), L, Qd, "wo")
             if self.tp is not None and self.tp.size > 1:
@@ -652,6 +657,7 @@ class LlamaModel:
                     cache.v_scale[i], cache.page_table, max_seq_bound,
                     self.scale, pos_state=pos_state, out=W.attn,
                     identity=cache.identity, split_blocks=self.split_blocks,
+                    window=c.sliding_window,
                 )
             else:
                 ops.attn_decode_paged(
@@ -659,6 +665,7 @@ class LlamaModel:
                     max_seq_bound, self.scale, pos_state=pos_state,
                     out=W.attn, identity=cache.identity,
                     split_blocks=self.split_blocks,
+                    window=c.sliding_window,
                 )
             if fused_f8:
                 gw = Qd.get("w_gate_up")

@@ -107,11 +107,14 @@ def attn_prefill(
     scale: Optional[float] = None,
     causal: bool = True,
     kv_offset: int = 0,
+    window: int = 0,
 ) -> torch.Tensor:
+    """window = W >= 1 (causal only) is a sliding window: the query at
+    absolute position i sees keys max(0, i - W + 1) .. i; 0 = off."""
     if _on_gpu(q):
         return _require_hip().attn_prefill(q, k, v, _attn_scale(q, scale),
-                                           causal, kv_offset)
-    return torch_ref.attn_prefill(q, k, v, scale, causal, kv_offset)
+                                           causal, kv_offset, window)
+    return torch_ref.attn_prefill(q, k, v, scale, causal, kv_offset, window)
 
 
 def attn_decode_paged(
@@ -125,6 +128,7 @@ def attn_decode_paged(
     out: Optional[torch.Tensor] = None,
     identity: bool = False,
     split_blocks: int = 0,
+    window: int = 0,
 ) -> torch.Tensor:
     """identity=True promises page_table[i] == i (the engine's single-pool
     cache): the split kernel then does pure address math — the per-lane
@@ -132,12 +136,16 @@ def attn_decode_paged(
     split_blocks>0 sets the split-grid block target (the engine passes its
     concurrency-aware pick; ADVSPEC_SPLIT_BLOCKS still overrides).
     With pos_state (graph mode) the true length is *pos_state + 1 in-kernel
-    and seq_len is the static max bound sizing the split geometry."""
+    and seq_len is the static max bound sizing the split geometry.
+    window = W >= 1 attends the last W positions only, [max(0, len - W), len);
+    the split geometry is then sized for min(seq_len, W + 63), whatever the
+    live length."""
     if _on_gpu(q):
         return _require_hip().attn_decode_paged(
             q, k_cache, v_cache, page_table, seq_len, _attn_scale(q, scale),
-            pos_state, out, identity, split_blocks)
-    return torch_ref.attn_decode_paged(q, k_cache, v_cache, page_table, seq_len, scale)
+            pos_state, out, identity, split_blocks, window)
+    return torch_ref.attn_decode_paged(q, k_cache, v_cache, page_table,
+                                       seq_len, scale, window)
 
 
 def kv_write(
@@ -226,6 +234,7 @@ def attn_decode_paged_fp8(
     out: Optional[torch.Tensor] = None,
     identity: bool = False,
     split_blocks: int = 0,
+    window: int = 0,
 ) -> torch.Tensor:
     """attn_decode_paged over an fp8 cache: same arguments plus the two
     scale tensors; the dequantization is folded into the split kernel (K
@@ -234,11 +243,13 @@ def attn_decode_paged_fp8(
     if _on_gpu(q):
         return _require_hip().attn_decode_paged_fp8(
             q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len,
-            _attn_scale(q, scale), pos_state, out, identity, split_blocks)
+            _attn_scale(q, scale), pos_state, out, identity, split_blocks,
+            window)
     if pos_state is not None:
         seq_len = int(pos_state.reshape(-1)[0]) + 1
     return torch_ref.attn_decode_paged_fp8(
-        q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len, scale)
+        q, k_cache, v_cache, k_scale, v_scale, page_table, seq_len, scale,
+        window)
 
 
 def kv_dequant_fp8(

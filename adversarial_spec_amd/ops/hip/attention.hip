@@ -112,13 +112,13 @@ attn_decode_split_kernel(
     const ushort_t *__restrict__ q,   // [hq, hd]
     const ushort_t *__restrict__ kc, const ushort_t *__restrict__ vc,
     const int *__restrict__ page_table, int seq_len, float scale,
-    int kh, int group, int hd, int page, int split_len,
+    int kh, int group, int hd, int page, int split_len, int window,
     float *__restrict__ ws_m, float *__restrict__ ws_l,
     float *__restrict__ ws_acc, const int *__restrict__ pos_ptr,
     ushort_t *__restrict__ out) {
   attn_decode_split_tiles<KvBf16<LPP * 8>, MG, IDENT>(
       {kc, vc}, q, page_table, seq_len, scale, kh, group, page, split_len,
-      ws_m, ws_l, ws_acc, pos_ptr, out);
+      window, ws_m, ws_l, ws_acc, pos_ptr, out);
 }
 
 
@@ -280,7 +280,8 @@ attn_decode_combine_kernel(const float *__restrict__ ws_m,
 // ---------------------------------------------------------------------------
 // Correctness-first causal prefill.
 // grid.x = hq, grid.y = ceil(tq / rows_per_block), block = 256 (4 waves).
-// Each 16-lane (LPP-lane) group owns ONE query row and walks keys 0..row.
+// Each 16-lane (LPP-lane) group owns ONE query row and walks keys 0..row, or
+// with a sliding window (window = W >= 1, causal only) keys row-W+1..row.
 // ---------------------------------------------------------------------------
 
 template <int LPP>
@@ -288,7 +289,7 @@ __global__ void __launch_bounds__(256) attn_prefill_simple_kernel(
     const ushort_t *__restrict__ q, const ushort_t *__restrict__ k,
     const ushort_t *__restrict__ v, ushort_t *__restrict__ out,
     int tq, int tk, int kv_offset, float scale, int hq, int kh, int hd,
-    int causal) {
+    int causal, int window) {
   const int h = blockIdx.x;
   const int g = h / (hq / kh);
   const int lane = threadIdx.x & (WAVE - 1);
@@ -299,6 +300,7 @@ __global__ void __launch_bounds__(256) attn_prefill_simple_kernel(
   if (row >= tq) return;
 
   const int limit = causal ? min(tk, kv_offset + row + 1) : tk;
+  const int first = window ? max(0, kv_offset + row - window + 1) : 0;
 
   float qf[8];
   {
@@ -312,7 +314,7 @@ __global__ void __launch_bounds__(256) attn_prefill_simple_kernel(
 #pragma unroll
   for (int j = 0; j < 8; ++j) acc[j] = 0.f;
 
-  for (int p = 0; p < limit; ++p) {
+  for (int p = first; p < limit; ++p) {
     const size_t kr = ((size_t)p * kh + g) * hd;
     const f32x8 kd = unpack8(((const bf16x8 *)(k + kr))[sl]);
     float dot = 0.f;
@@ -364,7 +366,8 @@ extern "C" void launch_attn_decode_split(const ushort_t *q, const ushort_t *kc,
                              decltype(IDENT)::value>
         <<<grid, 256, 0, stream>>>(  // all LDS is static in the kernel
             q, kc, vc, a.page_table, a.seq_len, a.scale, a.kh, a.group, a.hd,
-            a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr, out);
+            a.page, a.split_len, a.window, a.ws_m, a.ws_l, a.ws_acc,
+            a.pos_ptr, out);
   });
   if (a.n_splits > 1) {
     launch_attn_decode_combine(a.ws_m, a.ws_l, a.ws_acc, out, a.n_splits,
@@ -375,22 +378,22 @@ extern "C" void launch_attn_decode_split(const ushort_t *q, const ushort_t *kc,
 extern "C" void launch_attn_prefill_simple(
     const ushort_t *q, const ushort_t *k, const ushort_t *v, ushort_t *out,
     int tq, int tk, int kv_offset, float scale, int hq, int kh, int hd,
-    int causal, hipStream_t stream) {
+    int causal, int window, hipStream_t stream) {
   const int lpp = hd / 8;
   const int rows_per_block = 4 * (WAVE / lpp);
   dim3 grid(hq, (tq + rows_per_block - 1) / rows_per_block);
   switch (lpp) {
     case 4:
       attn_prefill_simple_kernel<4><<<grid, 256, 0, stream>>>(
-          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal);
+          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal, window);
       break;
     case 8:
       attn_prefill_simple_kernel<8><<<grid, 256, 0, stream>>>(
-          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal);
+          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal, window);
       break;
     case 16:
       attn_prefill_simple_kernel<16><<<grid, 256, 0, stream>>>(
-          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal);
+          q, k, v, out, tq, tk, kv_offset, scale, hq, kh, hd, causal, window);
       break;
   }
 }

@@ -44,6 +44,14 @@
 // Positions >= seq_len clamp to the last valid row when staged (their scores
 // are masked in compute), so nothing past the sequence is ever read.
 //
+// Sliding window (window = W >= 1): the block range moves, the ring does not.
+// With lo = max(0, seq_len - W) the splits tile [lo & ~(DTILE-1), seq_len),
+// so tile starts stay DTILE-aligned, and a lane is valid when lo <= position
+// < limit. Rows below lo inside the first tile are real cache rows that get
+// p = 0; they need no clamp. The host sizes the grid for min(bound, W + DTILE
+// - 1) positions, which covers that range at every live length. window = 0
+// gives lo = 0 and the walk from position 0.
+//
 // Workspace (fp32): ws_m, ws_l: [kh, n_splits, group]
 //                   ws_acc:     [kh, n_splits, group, hd]
 //
@@ -124,9 +132,10 @@ template <class KV, int MG, bool IDENT>
 DEVINL void attn_decode_split_tiles(
     const KV kv, const ushort_t *__restrict__ q,  // [hq, hd] bf16
     const int *__restrict__ page_table, int seq_len, float scale, int kh,
-    int group, int page, int split_len, float *__restrict__ ws_m,
-    float *__restrict__ ws_l, float *__restrict__ ws_acc,
-    const int *__restrict__ pos_ptr, ushort_t *__restrict__ out) {
+    int group, int page, int split_len, int window,
+    float *__restrict__ ws_m, float *__restrict__ ws_l,
+    float *__restrict__ ws_acc, const int *__restrict__ pos_ptr,
+    ushort_t *__restrict__ out) {
   constexpr int HD = KV::HD, EPL = KV::EPL, LPP = KV::LPP;
   constexpr int SUBS = WAVE / LPP;   // concurrent positions per PV step
   constexpr int NG = (MG + 3) / 4;   // GQA heads owned per wave
@@ -142,8 +151,9 @@ DEVINL void attn_decode_split_tiles(
   const int sl = lane % LPP;         // PV pass: dim slice within position
   const SplitWave w{page_table, seq_len, kh, page, g, wid, lane};
 
-  const int start = split * split_len;
-  const int limit = min(seq_len, (split + 1) * split_len);
+  const int lo = window ? max(0, seq_len - window) : 0;
+  const int start = (lo & ~(DTILE - 1)) + split * split_len;
+  const int limit = min(seq_len, start + split_len);
 
   // ONE shared array: [2 stage buffers] + the bf16 q image. The q image is
   // written by whole-wave 16-B glds pieces (64 lanes x 8 elements = 512
@@ -204,7 +214,7 @@ DEVINL void attn_decode_split_tiles(
       // ---- QK: lane-per-position full dot against the q image. A trait
       // does the work either in qk_chunks (K chunk outside, every head at
       // once, partial sums returned) or in qk_head (one head at a time). ----
-      const bool valid = tbase + lane < limit;
+      const bool valid = tbase + lane >= lo && tbase + lane < limit;
       const auto part = KV::template qk_chunks<NG>(buf, qlds, w, group);
 #pragma unroll
       for (int gi = 0; gi < NG; ++gi) {

@@ -17,6 +17,14 @@
 //      with the 16 consecutive-row banks distinct, not 8 scalar reads.
 //   P  [16][72] bf16 per wave (C->A layout bounce), same 144-B row pitch.
 //
+// Sliding window (WIN, window = W >= 1): query position i sees keys
+// max(0, i - W + 1) .. i. The block's tile walk starts at the KVBLK-aligned
+// tile holding the first key its FIRST row sees, so tiles wholly below the
+// window are never loaded, and the start depends only on the block's absolute
+// position: a chunked prefill whose chunks start on multiples of 128 walks
+// the tiles of the single-shot one. WIN is a template flag so that the
+// windowless kernel is compiled from the code it had before the flag.
+//
 // MFMA fragment maps (hardware-verified by tests/test_ops_gpu.py mfma probe):
 //   mfma_f32_16x16x32_bf16:
 //     A: lane l holds A[row = l%16][k = (l/16)*8 + j], j = 0..7
@@ -39,14 +47,14 @@ typedef __attribute__((__vector_size__(4 * sizeof(float)))) float f32x4v;
 // optimizing; rule 17 keeps stubbed values live via asm). 0 = full
 // kernel (the production path); 1 = no softmax (raw scores feed PV);
 // 2 = no P LDS bounce (reuse a fixed pfrag); 3 = no PV MFMAs.
-template <int ABL>
+template <int ABL, bool WIN>
 __global__ void __launch_bounds__(512, 1)
 attn_prefill_mfma_kernel(const ushort_t *__restrict__ q,
                          const ushort_t *__restrict__ k,
                          const ushort_t *__restrict__ v,
                          ushort_t *__restrict__ out, int tq, int tk,
                          int kv_offset, float scale, int hq, int kh,
-                         int causal) {
+                         int causal, int window) {
   const int h = blockIdx.x;
   const int g = h / (hq / kh);   // kv head
   const int qblock = blockIdx.y; // 128 q rows per block
@@ -142,8 +150,10 @@ attn_prefill_mfma_kernel(const ushort_t *__restrict__ q,
     }
   };
 
-  stage_load(0);
-  for (int kt = 0; kt < kmax; kt += KVBLK) {
+  const int kt0 =
+      WIN ? (max(0, kv_offset + qb0 - window + 1) & ~(KVBLK - 1)) : 0;
+  stage_load(kt0);
+  for (int kt = kt0; kt < kmax; kt += KVBLK) {
     __syncthreads();  // previous iteration's reads done
     stage_write();
     __syncthreads();
@@ -211,9 +221,12 @@ attn_prefill_mfma_kernel(const ushort_t *__restrict__ q,
     // ---- online softmax, lane-local row (row = lrow) ----
     // Interior tiles of a causal 8k+ walk are FULLY unmasked for the
     // whole wave (uniform predicate): skip the 32 mask compares there.
+    // With a window the tile's lowest key must also be inside the window
+    // of the wave's LAST row, the one whose window starts highest.
     const bool full_tile =
         (kt + KVBLK <= tk) &&
-        (!causal || kt + KVBLK <= kv_offset + q0 + 1);
+        (!causal || kt + KVBLK <= kv_offset + q0 + 1) &&
+        (!WIN || kt >= kv_offset + q0 + (QROWS - 1) - window + 1);
     // softmax runs in the LOG2-SCALED domain (exp2+fma fold, ladder
     // item): raw scores stay unscaled; m/l track m2 = m*scale*log2e and
     // p = exp2(fma(s_raw, scale2, -m2)) — one v_fma + v_exp per element
@@ -226,7 +239,8 @@ attn_prefill_mfma_kernel(const ushort_t *__restrict__ q,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           const int key = kt + n * 16 + lhi * 4 + r;
-          if (key >= tk || (causal && key > qrow_abs))
+          if (key >= tk || (causal && key > qrow_abs) ||
+              (WIN && key < qrow_abs - window + 1))
             s[n][r] = -INFINITY;
         }
       }
@@ -254,12 +268,17 @@ attn_prefill_mfma_kernel(const ushort_t *__restrict__ q,
     const float mn = defer ? m1 : fmaxf(m1, mx2);
     const float alpha =
         defer ? 1.0f : ((mn == -INFINITY) ? 0.f : exp2f(m1 - mn));
+    // Windowless, every row sees key 0 in the first tile, so mn is finite
+    // from there on. A row's window can lie wholly above the block's first
+    // tile(s): its scores are all -inf there while m1 still is, and
+    // fma(-inf, scale2, +inf) would be NaN where p must be 0.
+    const float mneg = (WIN && mn == -INFINITY) ? 0.f : -mn;
     float psum = 0.f;
 #pragma unroll
     for (int n = 0; n < 4; ++n) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float p = exp2f(__builtin_fmaf(s[n][r], scale2, -mn));
+        const float p = exp2f(__builtin_fmaf(s[n][r], scale2, mneg));
         s[n][r] = p;
         psum += p;
       }
@@ -329,14 +348,21 @@ extern "C" void launch_attn_prefill_mfma(const ushort_t *q, const ushort_t *k,
                                          const ushort_t *v, ushort_t *out,
                                          int tq, int tk, int kv_offset,
                                          float scale, int hq, int kh,
-                                         int hd, hipStream_t stream, int *ok) {
+                                         int hd, int window,
+                                         hipStream_t stream, int *ok) {
   if (hd != HD) {
     *ok = 0;
     return;
   }
   dim3 grid(hq, (tq + NWAVE * QROWS - 1) / (NWAVE * QROWS));
-  attn_prefill_mfma_kernel<0><<<grid, NWAVE * WAVE, 0, stream>>>(
-      q, k, v, out, tq, tk, kv_offset, scale, hq, kh, 1);
+  // a window that reaches back to key 0 from the last query row masks
+  // nothing: that is the windowless kernel
+  if (window > 0 && window < kv_offset + tq)
+    attn_prefill_mfma_kernel<0, true><<<grid, NWAVE * WAVE, 0, stream>>>(
+        q, k, v, out, tq, tk, kv_offset, scale, hq, kh, 1, window);
+  else
+    attn_prefill_mfma_kernel<0, false><<<grid, NWAVE * WAVE, 0, stream>>>(
+        q, k, v, out, tq, tk, kv_offset, scale, hq, kh, 1, 0);
   *ok = 1;
 }
 
@@ -348,8 +374,8 @@ extern "C" void launch_attn_prefill_mfma_abl(
   dim3 grid(hq, (tq + NWAVE * QROWS - 1) / (NWAVE * QROWS));
 #define ABL_CASE(N)                                                           \
   case N:                                                                     \
-    attn_prefill_mfma_kernel<N><<<grid, NWAVE * WAVE, 0, stream>>>(           \
-        q, k, v, out, tq, tk, 0, scale, hq, kh, 1);                           \
+    attn_prefill_mfma_kernel<N, false><<<grid, NWAVE * WAVE, 0, stream>>>(    \
+        q, k, v, out, tq, tk, 0, scale, hq, kh, 1, 0);                        \
     break;
   switch (abl) {
     ABL_CASE(0)

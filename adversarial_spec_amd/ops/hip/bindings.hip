@@ -290,7 +290,8 @@ void kv_write(torch::Tensor kc, torch::Tensor vc, torch::Tensor page_table,
 }
 
 torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                           double scale, bool causal, int64_t kv_offset) {
+                           double scale, bool causal, int64_t kv_offset,
+                           int64_t window) {
   CHECK_BF16_CUDA(q);
   CHECK_BF16_CUDA(k);
   CHECK_BF16_CUDA(v);
@@ -301,6 +302,10 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   const int tk = kc.size(0), kh = kc.size(1);
   TORCH_CHECK(hq % kh == 0, "GQA: hq % kh == 0");
   TORCH_CHECK(hd == 32 || hd == 64 || hd == 128, "hd in {32,64,128}");
+  TORCH_CHECK(window >= 0 && window <= INT32_MAX,
+              "attn_prefill: window >= 0");
+  TORCH_CHECK(causal || window == 0,
+              "attn_prefill: a sliding window needs causal=True");
   auto out = torch::empty_like(qc);
   // hd=128 causal takes the MFMA-tiled kernel; other head dims and the
   // non-causal path use the simple online-softmax kernel.
@@ -308,12 +313,12 @@ torch::Tensor attn_prefill(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   if (hd == 128 && causal) {
     launch_attn_prefill_mfma(uptr(qc), uptr(kc), uptr(vc), uptr_mut(out), tq,
                              tk, (int)kv_offset, (float)scale, hq, kh, hd,
-                             cur_stream(), &used_mfma);
+                             (int)window, cur_stream(), &used_mfma);
   }
   if (!used_mfma) {
     launch_attn_prefill_simple(uptr(qc), uptr(kc), uptr(vc), uptr_mut(out), tq,
                                tk, (int)kv_offset, (float)scale, hq, kh, hd,
-                               causal ? 1 : 0, cur_stream());
+                               causal ? 1 : 0, (int)window, cur_stream());
   }
   return out;
 }
@@ -331,7 +336,7 @@ torch::Tensor attn_prefill_simple(torch::Tensor q, torch::Tensor k,
   auto out = torch::empty_like(qc);
   launch_attn_prefill_simple(uptr(qc), uptr(kc), uptr(vc), uptr_mut(out), tq,
                              tk, (int)kv_offset, (float)scale, hq, kh, hd,
-                             causal ? 1 : 0, cur_stream());
+                             causal ? 1 : 0, 0, cur_stream());
   return out;
 }
 
@@ -372,8 +377,13 @@ torch::Tensor mfma_probe16(torch::Tensor a, torch::Tensor b) {
 // by per-wave SERIAL iterations (shfl-reduce + online-softmax chains), not
 // KV bytes, so occupancy (total blocks) is the lever; ADVSPEC_SPLIT_BLOCKS
 // overrides the target block count for A/B tuning on hardware.
-static void split_geometry(long seq, int kh, int target_blocks,
+// With a sliding window the kernel walks at most window + 63 positions (the
+// window plus the part of its first 64-position tile below it), so the
+// geometry is sized for that: it then depends on (bound, window, kh, target)
+// and never on the live position.
+static void split_geometry(long seq, int kh, int target_blocks, long window,
                            int* n_splits, int* split_len) {
+  if (window > 0) seq = std::min(seq, window + 63);
   // Target-block precedence: ADVSPEC_SPLIT_BLOCKS env (explicit A/B
   // override) > per-call target_blocks (the engine picks by its live
   // concurrency: solo decode wants ~512 blocks of self-occupancy, several
@@ -397,10 +407,12 @@ static void split_geometry(long seq, int kh, int target_blocks,
 // these arguments launches (ADVSPEC_SPLIT_BLOCKS override included), so a
 // test can assert the tile/split path it claims to exercise.
 py::tuple decode_split_geometry(int64_t seq, int64_t kh,
-                                int64_t split_blocks) {
+                                int64_t split_blocks, int64_t window) {
   TORCH_CHECK(seq >= 1 && kh >= 1, "decode_split_geometry: seq, kh >= 1");
+  TORCH_CHECK(window >= 0, "decode_split_geometry: window >= 0");
   int n_splits, split_len;
-  split_geometry(seq, (int)kh, (int)split_blocks, &n_splits, &split_len);
+  split_geometry(seq, (int)kh, (int)split_blocks, window, &n_splits,
+                 &split_len);
   return py::make_tuple(n_splits, split_len);
 }
 
@@ -421,7 +433,7 @@ static DecodeCall decode_prepare(const char* who, const torch::Tensor& q,
                                  int64_t bound, double scale,
                                  const OptTensor& pos_state,
                                  const OptTensor& out_opt, bool identity,
-                                 int64_t split_blocks) {
+                                 int64_t split_blocks, int64_t window) {
   CHECK_BF16_CUDA(q);
   TORCH_CHECK(q.dim() == 2, who, ": q [hq, hd]");
   DecodeCall c;
@@ -436,6 +448,10 @@ static DecodeCall decode_prepare(const char* who, const torch::Tensor& q,
       (identity ? kc.size(0) : page_table.numel()) * (int64_t)page;
   TORCH_CHECK(bound >= 1 && bound <= covered, who,
               ": seq_len outside the cache");
+  TORCH_CHECK(window >= 0, who, ": window >= 0");
+  // a window of the whole bound or more is no window; this also keeps the
+  // kernel's int32 argument in range
+  if (window >= bound) window = 0;
   const int* pos_ptr = check_pos_state(who, pos_state);
   if (out_opt.has_value()) {
     c.out = *out_opt;
@@ -447,12 +463,13 @@ static DecodeCall decode_prepare(const char* who, const torch::Tensor& q,
     c.out = torch::empty({hq, hd}, c.qc.options());
   }
   int n_splits, split_len;
-  split_geometry(bound, kh, (int)split_blocks, &n_splits, &split_len);
+  split_geometry(bound, kh, (int)split_blocks, window, &n_splits,
+                 &split_len);
   const long khnsg = (long)kh * n_splits * group;
   float* ws = decode_workspace(kc, khnsg, hd, q.device());
   c.a = {page_table.data_ptr<int>(), pos_ptr, (int)bound, (float)scale, kh,
          group, hd, page, split_len, n_splits, ws, ws + khnsg,
-         ws + 2 * khnsg, identity ? 1 : 0};
+         ws + 2 * khnsg, identity ? 1 : 0, (int)window};
   return c;
 }
 
@@ -461,11 +478,11 @@ torch::Tensor attn_decode_paged(torch::Tensor q, torch::Tensor kc,
                                 int64_t seq_len, double scale,
                                 const OptTensor& pos_state,
                                 const OptTensor& out, bool identity,
-                                int64_t split_blocks) {
+                                int64_t split_blocks, int64_t window) {
   check_kv_cache("attn_decode_paged", kc, vc, page_table);
   DecodeCall c =
       decode_prepare("attn_decode_paged", q, kc, page_table, seq_len, scale,
-                     pos_state, out, identity, split_blocks);
+                     pos_state, out, identity, split_blocks, window);
   launch_attn_decode_split(uptr(c.qc), uptr(kc), uptr(vc), c.a,
                            uptr_mut(c.out), cur_stream());
   return c.out;
@@ -478,11 +495,11 @@ torch::Tensor attn_decode_paged_fp8(torch::Tensor q, torch::Tensor kc,
                                     torch::Tensor page_table, int64_t seq_len,
                                     double scale, const OptTensor& pos_state,
                                     const OptTensor& out, bool identity,
-                                    int64_t split_blocks) {
+                                    int64_t split_blocks, int64_t window) {
   check_fp8_cache("attn_decode_paged_fp8", kc, vc, ksc, vsc, page_table);
   DecodeCall c =
       decode_prepare("attn_decode_paged_fp8", q, kc, page_table, seq_len,
-                     scale, pos_state, out, identity, split_blocks);
+                     scale, pos_state, out, identity, split_blocks, window);
   launch_attn_decode_split_fp8(uptr(c.qc), kc.data_ptr<uint8_t>(),
                                vc.data_ptr<uint8_t>(), ksc.data_ptr<float>(),
                                vsc.data_ptr<float>(), c.a, uptr_mut(c.out),
@@ -1163,7 +1180,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("kv_write", &kv_write, "paged KV scatter",
         py::arg("kc"), py::arg("vc"), py::arg("page_table"), py::arg("pos0"),
         py::arg("k"), py::arg("v"), py::arg("pos_state") = py::none());
-  m.def("attn_prefill", &attn_prefill, "causal prefill attention");
+  m.def("attn_prefill", &attn_prefill, "causal prefill attention",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("scale"),
+        py::arg("causal"), py::arg("kv_offset"), py::arg("window") = 0);
   m.def("attn_prefill_simple", &attn_prefill_simple, "non-MFMA prefill (anchor)");
   m.def("attn_prefill_ablate", &attn_prefill_ablate,
         "prefill attention perf-ablation variants");
@@ -1172,10 +1191,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("q"), py::arg("kc"), py::arg("vc"), py::arg("page_table"),
         py::arg("seq_len"), py::arg("scale"),
         py::arg("pos_state") = py::none(), py::arg("out") = py::none(),
-        py::arg("identity") = false, py::arg("split_blocks") = 0);
+        py::arg("identity") = false, py::arg("split_blocks") = 0,
+        py::arg("window") = 0);
   m.def("decode_split_geometry", &decode_split_geometry,
         "decode split geometry query -> (n_splits, split_len)",
-        py::arg("seq"), py::arg("kh"), py::arg("split_blocks") = 0);
+        py::arg("seq"), py::arg("kh"), py::arg("split_blocks") = 0,
+        py::arg("window") = 0);
   m.def("sample", &sample, "fused temperature softmax sample");
   m.def("sample_to", &sample_to, "async on-device sample into out[idx]");
   m.def("gemv", &gemv, "batch-1 decode GEMV (weight streaming)",
@@ -1253,7 +1274,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("vsc"), py::arg("page_table"), py::arg("seq_len"),
         py::arg("scale"), py::arg("pos_state") = py::none(),
         py::arg("out") = py::none(), py::arg("identity") = false,
-        py::arg("split_blocks") = 0);
+        py::arg("split_blocks") = 0, py::arg("window") = 0);
   m.def("ws_release", &ws_release,
         "drop decode-attention scratch for a dead KV cache");
 }

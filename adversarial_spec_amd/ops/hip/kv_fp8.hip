@@ -211,7 +211,19 @@ DEVINL void fp8x4_to_bf16x4(uint32_t w, uint32_t &p01, uint32_t &p23) {
                               0x07060302u);
 }
 
-template <int HD, int MG, bool IDENT>
+// WIN: the sliding-window range and its low-side compare are a template flag
+// here. As a run-time `window` (the bf16 skeleton's form, free there) hipcc
+// allocated this kernel's registers differently (hd=128 group 4: 102 -> 92
+// VGPRs, +70 instructions) and the windowless 8k solo call measured 5 %
+// slower (17.50 vs 16.64 us). With the flag off, `start` and `limit` are
+// the windowless expressions and `window` is the LAST argument, so no other
+// argument moves: every windowless instantiation is then the code it was
+// before the window existed, instruction for instruction, but for the offset
+// of one hidden kernel argument, and measures the same (16.66 vs 16.67 us;
+// profiles/r09_sliding_window.md). Formed as `0 + split * split_len` and
+// `start + split_len` with `window` in the middle of the list, the same
+// register counts still measured 16.94 us.
+template <int HD, int MG, bool IDENT, bool WIN>
 __global__ void __launch_bounds__(256) attn_decode_split_fp8_kernel(
     const ushort_t *__restrict__ q,   // [hq, hd] bf16
     const uint8_t *__restrict__ kc, const uint8_t *__restrict__ vc,
@@ -220,7 +232,7 @@ __global__ void __launch_bounds__(256) attn_decode_split_fp8_kernel(
     int kh, int group, int page, int split_len,
     float *__restrict__ ws_m, float *__restrict__ ws_l,
     float *__restrict__ ws_acc, const int *__restrict__ pos_ptr,
-    ushort_t *__restrict__ out) {
+    ushort_t *__restrict__ out, int window) {
   if (pos_ptr) seq_len = *pos_ptr + 1;  // graph mode, as the bf16 kernel
   constexpr int C16 = HD / 16;       // 16-B chunks per row = lanes per position
   constexpr int SUBS = WAVE / C16;   // rows per piece = positions per PV step
@@ -234,8 +246,16 @@ __global__ void __launch_bounds__(256) attn_decode_split_fp8_kernel(
   const int sub = lane / C16;
   const int sl = lane % C16;
 
-  const int start = split * split_len;
-  const int limit = min(seq_len, (split + 1) * split_len);
+  // sliding window: as the skeleton (see its header)
+  int lo = 0, start, limit;
+  if constexpr (WIN) {
+    lo = max(0, seq_len - window);
+    start = (lo & ~(DTILE - 1)) + split * split_len;
+    limit = min(seq_len, start + split_len);
+  } else {  // the windowless expressions, as they were before the window
+    start = split * split_len;
+    limit = min(seq_len, (split + 1) * split_len);
+  }
 
   // ONE shared array: [2 stage buffers][K | V | K scales | V scales] + the
   // bf16 q image (whole 1-KiB pieces, as in the bf16 kernel).
@@ -345,7 +365,8 @@ __global__ void __launch_bounds__(256) attn_decode_split_fp8_kernel(
 
       // ---- QK: lane-per-position full dot; the widened K chunk serves
       // every head this wave owns ----
-      const bool valid = tbase + lane < limit;
+      const bool valid =
+          (!WIN || tbase + lane >= lo) && tbase + lane < limit;
       const int myswz = kswz(lane);
       float a4[NG][4];
 #pragma unroll
@@ -495,12 +516,17 @@ extern "C" void launch_attn_decode_split_fp8(const ushort_t *q,
   const dim3 grid(a.kh, a.n_splits);
   dispatch_decode_split(a.hd, a.group, a.identity, [&](auto HD, auto MG,
                                                        auto IDENT) {
-    attn_decode_split_fp8_kernel<decltype(HD)::value, decltype(MG)::value,
-                                 decltype(IDENT)::value>
-        <<<grid, 256, 0, stream>>>(
-            q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,
-            a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc, a.pos_ptr,
-            out);
+    auto launch = [&](auto WIN) {
+      attn_decode_split_fp8_kernel<decltype(HD)::value, decltype(MG)::value,
+                                   decltype(IDENT)::value,
+                                   decltype(WIN)::value>
+          <<<grid, 256, 0, stream>>>(
+              q, kc, vc, ksc, vsc, a.page_table, a.seq_len, a.scale, a.kh,
+              a.group, a.page, a.split_len, a.ws_m, a.ws_l, a.ws_acc,
+              a.pos_ptr, out, a.window);
+    };
+    if (a.window > 0) launch(std::true_type{});
+    else launch(std::false_type{});
   });
   if (a.n_splits > 1) {
     // the bf16 path's combine pass (attention.hip), shared unchanged

@@ -41,6 +41,7 @@ struct DecodeSplitArgs {
   int split_len, n_splits;
   float *ws_m, *ws_l, *ws_acc;
   int identity;        // page_table[i] == i promised: skip the table read
+  int window;          // W >= 1: attend the last W positions only; 0 = all
 };
 
 // rope_kv / rope_kv_fp8 block size. decode (t <= 2): one wave per 64-thread
@@ -119,15 +120,17 @@ void launch_attn_decode_combine(const float *ws_m, const float *ws_l,
 void launch_attn_prefill_simple(const ushort_t *q, const ushort_t *k,
                                 const ushort_t *v, ushort_t *out, int tq,
                                 int tk, int kv_offset, float scale, int hq,
-                                int kh, int hd, int causal,
+                                int kh, int hd, int causal, int window,
                                 hipStream_t stream);
 
 // ---- attn_prefill_mfma.hip ------------------------------------------------
-// *ok = 0 and nothing launched when hd is not the kernel's 128
+// *ok = 0 and nothing launched when hd is not the kernel's 128. window =
+// W >= 1: query position i sees keys max(0, i - W + 1) .. i; 0 = no window
+// (launch_attn_prefill_simple takes the same argument, causal only).
 void launch_attn_prefill_mfma(const ushort_t *q, const ushort_t *k,
                               const ushort_t *v, ushort_t *out, int tq, int tk,
                               int kv_offset, float scale, int hq, int kh,
-                              int hd, hipStream_t stream, int *ok);
+                              int hd, int window, hipStream_t stream, int *ok);
 void launch_attn_prefill_mfma_abl(const ushort_t *q, const ushort_t *k,
                                   const ushort_t *v, ushort_t *out, int tq,
                                   int tk, float scale, int hq, int kh, int abl,

@@ -92,14 +92,19 @@ def attn_prefill(
     scale: Optional[float] = None,
     causal: bool = True,
     kv_offset: int = 0,
+    window: int = 0,
 ) -> torch.Tensor:
     """Full prefill attention with GQA.
 
     q: [tq, n_heads, hd]; k, v: [tk, n_kv_heads, hd]. Causal mask aligns
     query row i with absolute position kv_offset + i (for chunked prefill
     tk >= tq and earlier keys are always visible).
+    window = W >= 1 (causal only): the query at absolute position i sees
+    keys max(0, i - W + 1) .. i, W keys including itself; 0 = no window.
     Returns [tq, n_heads, hd].
     """
+    if window < 0 or (window and not causal):
+        raise ValueError("attn_prefill: window >= 0, and 0 unless causal")
     tq, h, hd = q.shape
     tk, kh, _ = k.shape
     if scale is None:
@@ -115,6 +120,8 @@ def attn_prefill(
         qpos = torch.arange(tq, device=q.device).unsqueeze(1) + kv_offset
         kpos = torch.arange(tk, device=q.device).unsqueeze(0)
         mask = kpos > qpos  # future keys
+        if window:
+            mask = mask | (kpos < qpos - window + 1)  # below the window
         scores = scores.masked_fill(mask.unsqueeze(0), float("-inf"))
     p = torch.softmax(scores, dim=-1)
     out = torch.bmm(p, vf)  # [h, tq, hd]
@@ -128,13 +135,17 @@ def attn_decode_paged(
     page_table: torch.Tensor,
     seq_len: int,
     scale: Optional[float] = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """Single-token decode attention over a paged KV cache.
 
     q: [n_heads, hd]; k_cache/v_cache: [n_pages, page_size, n_kv_heads, hd];
     page_table: int32 [n_used_pages] mapping logical page -> physical page.
-    Attends to positions [0, seq_len). Returns [n_heads, hd].
+    Attends to positions [0, seq_len), or with window = W >= 1 to
+    [max(0, seq_len - W), seq_len). Returns [n_heads, hd].
     """
+    if window < 0:
+        raise ValueError("attn_decode_paged: window >= 0")
     h, hd = q.shape
     npg, ps, kh, _ = k_cache.shape
     if scale is None:
@@ -143,6 +154,8 @@ def attn_decode_paged(
     phys = page_table[:n_used].long()
     k = k_cache[phys].reshape(n_used * ps, kh, hd)[:seq_len]  # [t, kh, hd]
     v = v_cache[phys].reshape(n_used * ps, kh, hd)[:seq_len]
+    if window:
+        k, v = k[max(0, seq_len - window):], v[max(0, seq_len - window):]
     group = h // kh
     qf = q.float()  # [h, hd]
     kf = k.float().repeat_interleave(group, dim=1).permute(1, 0, 2)  # [h, t, hd]
@@ -255,9 +268,11 @@ def attn_decode_paged_fp8(
     page_table: torch.Tensor,
     seq_len: int,
     scale: Optional[float] = None,
+    window: int = 0,
 ) -> torch.Tensor:
     """attn_decode_paged over the dequantized (fp32) positions [0, seq_len)
-    of an fp8 cache; nothing at or past seq_len is read."""
+    of an fp8 cache (the last `window` of them when window > 0); nothing at
+    or past seq_len is read."""
     ps = k_cache.shape[1]
     n_used = (seq_len + ps - 1) // ps
     k, v = kv_dequant_fp8(k_cache, v_cache, k_scale, v_scale, page_table,
@@ -269,7 +284,7 @@ def attn_decode_paged_fp8(
     ident = torch.arange(n_used, dtype=page_table.dtype, device=q.device)
     return attn_decode_paged(
         q, k.view(n_used, ps, *k.shape[1:]), v.view(n_used, ps, *v.shape[1:]),
-        ident, seq_len, scale)
+        ident, seq_len, scale, window)
 
 
 def sample(

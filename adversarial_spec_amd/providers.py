@@ -128,6 +128,7 @@ LOCAL_MODEL_MAP: dict[str, str] = {
     "llama-3.1-8b": "llama-3-8b",
     "llama-3.1-70b": "llama-3-70b",
     "mistral-7b": "mistral-7b",
+    "mistral-7b-v0.1": "mistral-7b-v0.1",  # 4096-token sliding window
     "tiny": "tiny",          # 4-layer CPU test model
     "debug-1b": "debug-1b",  # 16-layer GPU smoke/test model
 }
@@ -523,13 +524,25 @@ def validate_sampling_filter(top_p: Any, top_k: Any) -> tuple[float, int]:
     return float(top_p), int(top_k)
 
 
+def validate_sliding_window(window: Any, source: str = "sliding_window") -> int:
+    """A sliding attention window as an int: 0 = off, W >= 1 = each position
+    attends its last W keys, itself included. Bools, non-integers, negatives
+    and values past int32 are a ValueError naming `source`."""
+    if (isinstance(window, bool) or not isinstance(window, int)
+            or not 0 <= window < 2**31):
+        raise ValueError(
+            f"sliding_window must be an integer >= 0, got {window!r} ({source})")
+    return window
+
+
 def handle_local_command(subcommand: Optional[str], arg: Optional[str],
                          extra: Optional[str], weights: Optional[str],
                          gpu: Optional[int],
                          dtype: Optional[str] = None,
                          kv_dtype: Optional[str] = None,
                          top_p: Optional[float] = None,
-                         top_k: Optional[int] = None) -> int:
+                         top_k: Optional[int] = None,
+                         sliding_window: Optional[int] = None) -> int:
     """`debate.py local {status,add-model,remove-model,alias,list-models}` —
     manages the MI355X model registry section of the global config."""
     config = load_global_config()
@@ -574,7 +587,8 @@ def handle_local_command(subcommand: Optional[str], arg: Optional[str],
     if subcommand == "alias":
         if not arg or not extra:
             print("Error: usage: local alias <name> <arch> [--weights PATH] [--gpu N] "
-                  "[--top-p F] [--top-k N]", file=sys.stderr)
+                  "[--top-p F] [--top-k N] [--sliding-window N]",
+                  file=sys.stderr)
             return 1
         if extra not in LOCAL_MODEL_MAP and extra not in LOCAL_MODEL_MAP.values():
             print(f"Error: unknown arch '{extra}'", file=sys.stderr)
@@ -588,6 +602,12 @@ def handle_local_command(subcommand: Optional[str], arg: Optional[str],
             spec["dtype"] = dtype
         if kv_dtype:
             spec["kv_dtype"] = kv_dtype
+        if sliding_window is not None:
+            try:
+                spec["sliding_window"] = validate_sliding_window(sliding_window)
+            except ValueError as e:
+                print(f"Error: {e}", file=sys.stderr)
+                return 1
         if top_p is not None or top_k is not None:
             # sampling defaults of the alias; only the given ones are stored
             try:

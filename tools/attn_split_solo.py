@@ -2,7 +2,7 @@
 (kernel-trace or PMC) or timed on its own.
 
     attn_split_solo.py [seq] [iters] [--kv-dtype bf16|fp8] [--identity]
-                       [--split-blocks N]
+                       [--split-blocks N] [--window W]
 
 After 10 eager warm-up calls the kernels run from HIP-GRAPH REPLAY: 20 calls
 are captured once and the graph is replayed, so a profiler sees graph-launched
@@ -10,7 +10,8 @@ kernels and `iters` is rounded down to a multiple of 20 (at least 20). The
 mean time per call (HIP events around the replays) is printed, so the bf16
 and fp8 KV paths can be compared without a profiler. `kv_bytes` is what one
 call reads from the cache: K and V rows, plus the scale tensors for fp8
-(`scale_bytes`, about 3 % of the fp8 total at hd=128).
+(`scale_bytes`, about 3 % of the fp8 total at hd=128); with `--window` only
+the rows the windowed call stages are counted.
 """
 import argparse
 import os
@@ -29,6 +30,8 @@ ap.add_argument("--kv-dtype", choices=["bf16", "fp8"], default="bf16")
 ap.add_argument("--identity", action="store_true",
                 help="identity page table (the engine's single-pool cache)")
 ap.add_argument("--split-blocks", type=int, default=0)
+ap.add_argument("--window", type=int, default=0,
+                help="sliding window: attend the last W positions only")
 args = ap.parse_args()
 
 torch.manual_seed(7)
@@ -42,7 +45,7 @@ q = torch.randn(kh * group, hd, device="cuda").bfloat16()
 pos = torch.tensor([seq - 1], dtype=torch.int32, device="cuda")
 out = torch.empty(kh * group, hd, device="cuda").bfloat16()
 kw = dict(pos_state=pos, out=out, identity=args.identity,
-          split_blocks=args.split_blocks)
+          split_blocks=args.split_blocks, window=args.window)
 if args.kv_dtype == "fp8":
     kc, ks = torch_ref.quantize_kv_fp8(kc)
     vc, vs = torch_ref.quantize_kv_fp8(vc)
@@ -75,7 +78,13 @@ for _ in range(reps):
     graph.replay()
 t1.record()
 torch.cuda.synchronize()
-scale_bytes = 2 * seq * kh * 4 if args.kv_dtype == "fp8" else 0
-kv_bytes = 2 * seq * kh * hd * kc.element_size() + scale_bytes
+# rows one call stages: with a window, from the 64-aligned tile that holds
+# position seq - W (at most W + 63 rows), else the whole context
+rows = seq
+if 0 < args.window < seq:
+    rows = seq - (seq - args.window) // 64 * 64
+scale_bytes = 2 * rows * kh * 4 if args.kv_dtype == "fp8" else 0
+kv_bytes = 2 * rows * kh * hd * kc.element_size() + scale_bytes
 print(f"done {seq} {iters} kv_dtype={args.kv_dtype} identity={args.identity} "
+      f"window={args.window} "
       f"kv_bytes={kv_bytes} scale_bytes={scale_bytes} us_per_call={t0.elapsed_time(t1) * 1e3 / iters:.2f}")
