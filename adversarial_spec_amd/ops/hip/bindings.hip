@@ -705,9 +705,18 @@ void gemv_gateup_norm(torch::Tensor x, torch::Tensor wln, torch::Tensor w,
                           F2 / 2, (float)eps, cur_stream());
 }
 
+// The 8-phase 256^2 tile loop for prefill-sized shapes (its counted-vmcnt
+// schedule needs K % 128 == 0 and K >= 512, and it
+// pays off when the M/N tiles fill); the 128^2 loop covers everything else.
+// One rule for the bf16 and the fp8 GEMM.
+static bool use_gemm256(int M, int N, int K) {
+  return M > 128 && N >= 256 && K >= 512 && (K % 128) == 0;
+}
+
 // Operands of the bf16 prefill GEMMs, checked before anything is allocated
 // or launched. The kernels stage A and B in 16-byte chunks of 8 elements, so
-// K % 8 == 0 keeps every row 16-byte aligned and leaves no sub-chunk tail.
+// K % 8 == 0 keeps every row 16-byte aligned and leaves no sub-chunk tail
+// (gemm_tiles.h, "K contract": stage_edge has no element-wise arm).
 static void check_gemm_operands(const char* who, const torch::Tensor& a,
                                 const torch::Tensor& b) {
   TORCH_CHECK(a.is_cuda() && a.scalar_type() == at::kBFloat16 && a.dim() == 2,
@@ -719,7 +728,7 @@ static void check_gemm_operands(const char* who, const torch::Tensor& a,
 }
 
 // Tiled MFMA GEMM: C = A @ B, bf16, fp32 accumulation. Replaces library
-// GEMMs on the prefill path (deterministic, workspace-free; see gemm.hip).
+// GEMMs on the prefill path (deterministic, workspace-free; see gemm_tiles.h).
 torch::Tensor gemm(torch::Tensor a, torch::Tensor b) {
   // C = a @ b^T with b stored row-major [N, K] (HF layout)
   check_gemm_operands("gemm", a, b);
@@ -727,10 +736,7 @@ torch::Tensor gemm(torch::Tensor a, torch::Tensor b) {
   auto bc = b.contiguous();
   const int M = ac.size(0), K = ac.size(1), N = bc.size(0);
   auto c = torch::empty({M, N}, ac.options());
-  // Deep-pipelined 256^2 8-phase kernel for prefill-sized shapes (its
-  // counted-vmcnt schedule needs K % 128 == 0 and pays off when the M/N
-  // tiles fill); the 128^2 kernel covers everything else.
-  if (M > 128 && N >= 256 && K >= 512 && (K % 128) == 0) {
+  if (use_gemm256(M, N, K)) {
     launch_gemm256(uptr(ac), uptr(bc), uptr_mut(c), M, N, K, cur_stream());
   } else {
     launch_gemm(uptr(ac), uptr(bc), uptr_mut(c), M, N, K, cur_stream());
@@ -782,7 +788,8 @@ void quant_fp8(torch::Tensor x, torch::Tensor q, torch::Tensor scale) {
 // Operands shared by the fp8 GEMM and the fp8 decode GEMVs, checked before
 // any launch. The kernels stream w8 and x8 in 16-byte chunks of 16 codes
 // (nc = K / 16), so a K that is no multiple of 16 would silently drop the row
-// tails (and, in the GEMM, leave its 16-byte loads only 8-byte aligned).
+// tails (and, in the GEMM, leave its 16-byte loads only 8-byte aligned;
+// gemm_tiles.h, "K contract": stage_edge copies whole chunks, no byte loop).
 static void check_fp8_weight(const char* who, const torch::Tensor& w8,
                              const torch::Tensor& wsc) {
   TORCH_CHECK(w8.is_cuda() && w8.scalar_type() == at::kByte && w8.dim() == 2 &&
@@ -810,9 +817,7 @@ torch::Tensor gemm_fp8(torch::Tensor x, torch::Tensor w8, torch::Tensor wsc) {
   launch_quant_fp8(uptr(xc), x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                    M, K, cur_stream());
   auto c = torch::empty({M, N}, xc.options());
-  // 8-phase 256^2 kernel for prefill-sized shapes (same dispatch rule as
-  // the bf16 gemm); 128^2 covers edges and small shapes.
-  if (M > 128 && N >= 256 && K >= 512 && (K % 128) == 0) {
+  if (use_gemm256(M, N, K)) {
     launch_gemm_fp8_256(x8.data_ptr<uint8_t>(), xs.data_ptr<float>(),
                         w8.data_ptr<uint8_t>(), wsc.data_ptr<float>(),
                         uptr_mut(c), M, N, K, cur_stream());

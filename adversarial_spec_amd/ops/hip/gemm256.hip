@@ -1,47 +1,15 @@
-// Deep-pipelined 256x256 MFMA GEMM for CDNA4 (gfx950):
-// C[M,N] = A[M,K] @ B[N,K]^T, bf16 in/out, fp32 accumulation.
-//
-// This is the 8-phase 256^2 structure from cdna_hip_programming.md §5
-// ("The 256^2 8-phase template"): the 128^2 two-barrier kernel (gemm.hip)
-// ceilings at ~900 TF/s because the workgroup-release inside its
-// __syncthreads drains the global_load_lds queue (vmcnt(0)) every K-step.
-// Here the staging loads SPAN barriers behind a counted s_waitcnt:
-//
-//   - tile 256x256, BK=64, 8 waves (2M x 4N), one block per CU;
-//   - LDS = 128 KiB: 2 buffers x 4 half-images [128][64] bf16
-//     (A rows 0-127, A rows 128-255, B rows 0-127, B rows 128-255);
-//   - 4 phases per K-tile; each phase: {ds_read a fragment subtile,
-//     glds-prefetch ONE half-tile of a future K-tile, raw s_barrier,
-//     lgkmcnt(0), setprio(1), 16 MFMA (one C-quadrant x K=64),
-//     setprio(0), raw s_barrier};
-//   - half-tiles are staged 6 phases ahead of first use; the ONLY vmcnt
-//     in the main loop is a counted vmcnt(4) once per K-tile (two
-//     half-tiles = 4 glds/wave stay in flight across every barrier);
-//     the last boundary drains (vmcnt 0) and the epilogue stores.
-//
-// Schedule invariant (why vmcnt(4) is correct): stages issue one
-// half-tile per phase in order S = 4*tile + half (phase 0 of tile t
-// stages (t+1, B_lo), phase 1 (t+1, B_hi), phase 2 (t+2, A_lo), phase 3
-// (t+2, A_hi)); the wait at the end of tile t's phase 3 must cover every
-// half of tile t+1. (t+1, h3) is issued at phase 4t+1, and exactly two
-// stages — (t+2, h0), (t+2, h1) — follow it before the wait, so "all but
-// the newest 4 loads" == "tile t+1 fully landed". Image overwrite is
-// safe because a buffer's images are last READ in phases 0-1 of their
-// tile (all fragment ds_reads happen there) and first REWRITTEN 4+
-// phases later. The tail tiles are peeled as template specializations so
-// the main loop carries NO stage guards: a guarded variant spilled 3
-// VGPRs and hipcc's spill-reload wait (vmcnt(0)) drained the pipeline
-// every iteration.
-//
-// Swizzle: identical to gemm.hip — glds writes lane-linear, so the
-// bank-conflict XOR (chunk ^= row&7) is applied to the per-lane GLOBAL
-// source address (within one 128-B cacheline, coalescing preserved) and
-// de-swizzled on the fragment ds_read (guide §5.4 rule 21).
-//
-// Edge handling: M/N edges CLAMP the per-lane source row (reads stay in
-// bounds; garbage rows only feed C rows/cols that the guarded epilogue
-// never stores). K must be a multiple of 128 and >= 512 — the dispatcher
-// (bindings.hip gemm()) falls back to gemm.hip otherwise.
+// Deep-pipelined 256x256 bf16 MFMA GEMM (gemm_nt256_kernel): the 8-phase loop
+// that gemm_tiles.h describes (schedule invariant, swizzle, edge clamp, the one
+// __shared__ array), here still WRITTEN OUT as it was before gemm256_tiles<T>
+// existed. gemm256_tiles<TileBf16> is the same program and gives bit-identical
+// results, but at 254 VGPRs and 512 threads this kernel is the tightest of the
+// four: called through gemm256_tiles::run it compiled one instruction longer
+// in the main loop and missed the speed gate in the paired probe, and so did
+// its body written into the kernel over the shared helpers
+// (profiles/r10_gemm_skeleton.md). Until that is understood this file compiles
+// to the code it always had. A schedule change made in gemm256_tiles is to be
+// made here too. Nothing here is shared with gemm_tiles.h; g2_stage / g2_tile
+// correspond to its stage / tile.
 
 #include "common.h"
 #include "launchers.h"
@@ -208,8 +176,7 @@ gemm_nt256_kernel(const ushort_t *__restrict__ a,
   const int m0 = blockIdx.y * G2_BM;
   const int nt = K / G2_BK;     // K % 128 == 0, K >= 512 (dispatcher)
 
-  // ONE shared array (a second __shared__ object de-pipelines glds —
-  // guide §5 ".s-level traps" (a)).
+  // ONE shared array (see gemm_tiles.h).
   __shared__ __attribute__((aligned(16))) ushort_t lds[2 * 4 * G2_IMG];
 
   // Per-lane stage source pointers at k=0, one per (half-image, issue):

@@ -185,7 +185,7 @@ void launch_gemm(const ushort_t *a, const ushort_t *b, ushort_t *c, int M,
 void launch_gemm256(const ushort_t *a, const ushort_t *b, ushort_t *c, int M,
                     int N, int K, hipStream_t stream);
 
-// ---- gemm_fp8.hip, gemm256_fp8.hip: e4m3 operands + per-row f32 scales ----
+// ---- gemm_fp8.hip (128^2, 256^2): e4m3 operands + per-row f32 scales ----
 void launch_gemm_fp8(const uint8_t *a, const float *asc, const uint8_t *b,
                      const float *bsc, ushort_t *c, int M, int N, int K,
                      hipStream_t stream);

@@ -30,7 +30,6 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "gemm.hip"),
         os.path.join(HIP_DIR, "gemm256.hip"),
         os.path.join(HIP_DIR, "gemm_fp8.hip"),
-        os.path.join(HIP_DIR, "gemm256_fp8.hip"),
         os.path.join(HIP_DIR, "sampling.hip"),
         os.path.join(HIP_DIR, "mfma_rate.hip"),
     ],
@@ -41,6 +40,7 @@ ext = CUDAExtension(
         os.path.join(HIP_DIR, "rope_epilogue.h"),
         os.path.join(HIP_DIR, "gemv_rows.h"),
         os.path.join(HIP_DIR, "attn_decode_split.h"),
+        os.path.join(HIP_DIR, "gemm_tiles.h"),
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],

@@ -1,7 +1,9 @@
 """Helpers shared by test_gemm_exact_cpu.py and test_gemm_exact_gpu.py: the
-staging paths of the four prefill MFMA GEMMs (ops/hip/gemm.hip, gemm256.hip,
-gemm_fp8.hip, gemm256_fp8.hip), the shape lists that pin each of them, inputs
-for which their fp32 accumulation is exact, references, and a gather probe.
+staging paths of the four prefill MFMA GEMMs (the two tile loops of
+ops/hip/gemm_tiles.h, instantiated in gemm.hip and gemm_fp8.hip, and the bf16
+256^2 loop written out in gemm256.hip), the shape lists that pin each of
+them, inputs for which their fp32 accumulation is exact, references, and a
+gather probe.
 Everything here runs on the CPU and depends on torch alone."""
 
 import functools
@@ -22,8 +24,9 @@ FP8_PIN = 448.0           # the e4m3 maximum: one per row fixes the row scale
 # ---- the dispatch rule and the paths a shape takes ---------------------------
 
 def dispatch256(M, N, K):
-    """gemm() and gemm_fp8() in ops/hip/bindings.hip: True -> the 256^2
-    8-phase kernel, False -> the 128^2 two-barrier kernel."""
+    """use_gemm256() in ops/hip/bindings.hip, which gemm() and gemm_fp8() both
+    call: True -> the 256^2 8-phase kernel, False -> the 128^2 two-barrier
+    kernel."""
     return M > 128 and N >= 256 and K >= 512 and K % 128 == 0
 
 

@@ -1,6 +1,6 @@
-"""The four prefill MFMA GEMMs (ops/hip/gemm.hip, gemm256.hip, gemm_fp8.hip,
-gemm256_fp8.hip) at their tile, K-tail and dispatch edges, without a numeric
-tolerance.
+"""The four prefill MFMA GEMMs (ops/hip/gemm_tiles.h; entries in gemm.hip and
+gemm_fp8.hip; gemm256.hip) at their tile, K-tail and dispatch edges, without a
+numeric tolerance.
 
   - Small-integer inputs make every fp32 partial sum exact in any order
     (tests/gemm_exact_common.py; the premises and the coverage of the shape

@@ -428,7 +428,7 @@ class TestGemm256:
                 assert torch.equal(again, first), "gemm256 nondeterminism"
 
     def test_fp8_256_vs_dequant_ref_and_race(self):
-        """fp8 8-phase variant (gemm256_fp8.hip): CPU dequant parity at a
+        """fp8 8-phase variant (gemm256_tiles<TileE4m3>): CPU dequant parity at a
         256-dispatch shape + bitwise rerun stability."""
         m, n, k = 512, 768, 640
         x = _bf(torch.randn(m, k)).to(DEV)
